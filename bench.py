@@ -14,7 +14,13 @@ batches already resident in HBM; it is the very iteration `Solver.fit` runs (Sol
         bench.py --gpus N --steps K --warmup W
 
 Prints ONE JSON line (rank 0). Timed region: K steps between two HIP events recorded on the launch stream, bracketed
-by a barrier + device synchronise on both sides; the MAX over ranks is reported. `roofline`: algorithmic FLOPs of the
+by a barrier + device synchronise on both sides; the MAX over ranks is reported. A plain run does only what that headline
+needs: set-up, the --settle load, W warm-up steps, the K timed steps, the line. `--full` adds every side measurement and
+check below (oracle parity, `cold`, `sustained`, `strong`, all-reduce time, the bf16x3 side figure, roofline, CPU baseline,
+`baseline_configs`). `--dump-outputs DIR` writes what the last timed step computed (parameters after its Adam update,
+gradients, loss) as DIR/<name>.npy; the inputs are seeded, so two builds can be compared output for output.
+
+`roofline` (--full): algorithmic FLOPs of the
 step's matrix kernels per launch = F * points, F = 6*S*sum_{l>=2}(in*out) + 4*d*H1, over their mean
 duration measured with HIP events on the launch stream (pinn_profile_tile), against the fp32 MFMA peak of MI355X
 (157.3 TFLOP/s). `cpu_baseline`: the oracle restatement of the reference step (oracle/pinn_oracle.py, torch CPU ops)
@@ -329,6 +335,32 @@ def wgrad_split(name):
     return len(fields) > 5 and fields[5] == 'true'
 
 
+def step_outputs(solver):
+    """ what a caller of the timed step receives from its last call, as host float32 arrays in the order of model.parameters()
+    (weights and biases layer by layer, log_scale, trainable V(...) scalars): `params` after the step's Adam update, `grads` of
+    that step, and its `loss`. At most a few MB for every workload here (the widest, poisson512, has 0.8 M parameters). """
+    model = solver.model
+    lay = model.net.layout
+
+    def gather(buf):
+        parts = []
+        for w, b in model.net.param_views(buf):
+            parts += [w.reshape(-1), b.reshape(-1)]
+        parts.append(buf[lay.off_log_scale].reshape(1))
+        for off, n in getattr(model, 'variables', {}).values():
+            parts.append(buf[off:off + n].reshape(-1))
+        return torch.cat(parts).detach().to('cpu', torch.float32).numpy()
+
+    return {'params': gather(model.flat), 'grads': gather(solver.grads),
+            'loss': solver.grads[lay.off_loss].detach().to('cpu', torch.float32).numpy().reshape(1)}
+
+
+def dump_outputs(out_dir, outputs):
+    os.makedirs(out_dir, exist_ok=True)
+    for name, arr in outputs.items():
+        np.save(os.path.join(out_dir, f'{name}.npy'), arr)
+
+
 def relaunch(n_gpus):
     import socket
     with socket.socket() as sock:
@@ -338,7 +370,9 @@ def relaunch(n_gpus):
            '--master-addr', '127.0.0.1', '--master-port', str(port), os.path.abspath(__file__), *sys.argv[1:]]
     print('[bench] no WORLD_SIZE in the environment: launching ' + ' '.join(cmd), file=sys.stderr, flush=True)
     sys.stdout.flush()
-    os.execv(sys.executable, cmd)
+    # (a child process, not an exec: this process has loaded the HIP runtime already)
+    import subprocess
+    sys.exit(subprocess.run(cmd).returncode)
 
 
 def main():
@@ -373,10 +407,16 @@ def main():
                     help='skip the `cold` pass (the same W + K steps taken first, before the --settle load): tools/profile_bench.sh, so '
                          'that the average duration of a profile is the settled one')
     ap.add_argument('--no-configs', action='store_true',
-                    help='skip the compact `baseline_configs` object of the default run (cfg1 fit rate, cfg3 / cfg4 / cfg5 step time, roofline '
+                    help='skip the compact `baseline_configs` object of a --full run (cfg1 fit rate, cfg3 / cfg4 / cfg5 step time, roofline '
                          'fractions and parity) and the `sustained` figure: tools/profile_bench.sh')
     ap.add_argument('--unfused', action='store_true',
                     help='diagnostic: run the N > 1 step path (step, all-reduce, Adam as separate launches) at N = 1')
+    ap.add_argument('--full', action='store_true',
+                    help='besides the headline, every side measurement and check: oracle parity before / after the timed steps, the `cold` '
+                         'pass, `sustained`, `strong`, the all-reduce time, the bf16x3 side figure, per-kernel durations and roofline, the '
+                         'CPU baseline and `baseline_configs` (the --no-* options above switch parts of it off)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write what the last timed step computed (params after its Adam update, grads, loss: float32) as DIR/<name>.npy')
     args = ap.parse_args()
     freeze_once()
 
@@ -450,7 +490,7 @@ def main():
     pool = make_pool(n)
     # BEFORE anything is timed: the step path of this run against the oracle on 4 096 points at the initial parameters (rank 0)
     parity_at_start = None
-    if rank == 0 and not on_cpu and not args.lib and not args.no_parity:
+    if args.full and rank == 0 and not on_cpu and not args.lib and not args.no_parity:
         parity_at_start = parity_check(args.workload, solver, generic, nn_mse())
 
     from pydens_amd.solver import FlatAdam
@@ -522,7 +562,7 @@ def main():
     # DESIGN.md section 6a.
     cold = None
     if args.settle > 0 and not on_cpu:
-        if not args.no_cold:
+        if args.full and not args.no_cold:
             cold_dt, cold_host = timed(pool, warmup, steps)
             cold = {'ms_per_step': cold_dt / steps * 1e3, 'value': n * world * steps / cold_dt,
                     'what': f'the same {warmup} + {steps} steps taken first, in the fresh process, before the --settle load'}
@@ -536,10 +576,12 @@ def main():
         del a, b
     dt, host_dt = timed(pool, warmup, steps)
     loss = float(solver.grads[lay.off_loss].item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, step_outputs(solver))        # (before anything below takes further steps)
     rank_ms = [x / steps * 1e3 for x in per_rank]
     # one SUSTAINED figure: >= 2 000 steps in one timed region, no preparation of its own -- what a training run sees
     sustained = None
-    if not on_cpu and not args.no_configs and args.workload in ('cfg2', 'cfg4') and not args.lib:
+    if args.full and not on_cpu and not args.no_configs and args.workload in ('cfg2', 'cfg4') and not args.lib:
         s_steps = 2000
         s_dt, _ = timed(pool, 0, s_steps)
         sustained = {'steps': s_steps, 'ms_per_step': s_dt / s_steps * 1e3, 'value': n * world * s_steps / s_dt,
@@ -547,7 +589,7 @@ def main():
     # the gradient all-reduce by itself: K back-to-back all-reduces of the flat gradient buffer between two HIP events on the compute
     # stream, MAX over the ranks (what one iteration pays for communication when nothing overlaps it)
     allreduce_us = None
-    if dp and not on_cpu:
+    if args.full and dp and not on_cpu:
         for _ in range(5):
             solver._all_reduce(stream)
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -569,7 +611,7 @@ def main():
     # same run as a side figure (its own point pool, same step path); the headline stays the per-GPU batch of the workload
     strong = None
     strong_total = 1048576
-    if not args.no_strong and not args.global_points and not args.batch and args.workload == 'cfg2' and not on_cpu \
+    if args.full and not args.no_strong and not args.global_points and not args.batch and args.workload == 'cfg2' and not on_cpu \
             and strong_total % world == 0:
         ns = strong_total // world
         spool = make_pool(ns)
@@ -582,7 +624,10 @@ def main():
     # matrix-kernel durations, measured live with HIP events around the launches (separate pass, same stream)
     tile_ms = wgrad_ms = None
     kernel = wgrad_kernel = ''
-    if rank == 0:
+    if rank == 0 and not args.full:
+        kernel = model.net.lib.pinn_last_kernel_name().decode()           # (the `dtype` of the line names the kernels' arithmetic)
+        wgrad_kernel = model.net.lib.pinn_last_wgrad_kernel_name().decode()
+    elif rank == 0:
         lib = model.net.lib
         lib.pinn_profile_tile(1)
         s_tile, s_wg = [], []
@@ -604,9 +649,9 @@ def main():
         dist.barrier()
 
     # the gated split-bf16 GEMM variant (pinn_set_gemm_mode; `--gemm bf16x3` makes it the headline of a run of its own) as a side
-    # figure of the default run: the same W + K steps on the same pool, after everything that describes the fp32 kernels
+    # figure of a --full run: the same W + K steps on the same pool, after everything that describes the fp32 kernels
     side_split = None
-    if args.gemm == 'fp32' and args.workload in BASELINE_WORKLOADS and not on_cpu and not generic and not args.lib and not args.no_side:
+    if args.full and args.gemm == 'fp32' and args.workload in BASELINE_WORKLOADS and not on_cpu and not generic and not args.lib and not args.no_side:
         solver.set_gemm_mode('bf16x3')
         b_dt, _ = timed(pool, warmup, steps)
         if rank == 0:
@@ -620,54 +665,57 @@ def main():
     comm_info = solver._comm.describe() if (dp and solver._comm is not None) else None
     out = None
     if rank == 0:
-        print(f'[bench] gpu: {dt / steps * 1e3:.4f} ms/step by HIP events ({host_dt / steps * 1e3:.4f} by the host clock), '
-              f'tile kernel {tile_ms:.4f} ms' + (f', wgrad kernel {wgrad_ms:.4f} ms' if wgrad_ms else ''), file=sys.stderr)
-        # algorithmic FLOPs: the reference's formulation (one stream per derivative D(...) asks for). The
-        # kernels propagate the second derivatives a Laplacian / wave / heat operator needs as ONE combined stream, so the
-        # matrix pipe executes S_exec / S of that figure; both are reported.
-        f_pt = flops_per_point(model.layer_dims, spec.n_streams)
-        plan = solver.residual_plan
-        s_exec = (2 + spec.nd) if (plan is not None and plan.comb_w is not None and not generic) else spec.n_streams
-        f_exec = flops_per_point(model.layer_dims, s_exec)
-        roof_note = None
-        if generic and len(spec.groups) > 1:
-            # direction groups (width 512, many directions): kernel_ms is the LAST backward launch -- one group's streams -- so the FLOPs it is
-            # priced with are that group's too (the whole-step count over one launch's time read 1.09 of the peak on poisson512)
-            s_exec = len(spec.groups[-1][2])
-            f_pt = f_exec = flops_per_point(model.layer_dims, s_exec)
-            roof_note = ('generic path in %d direction groups: kernel_ms, flops_per_point and frac describe the LAST pinn_jet_backward launch '
-                         '(the %d streams of its group); `value` is the whole step' % (len(spec.groups), s_exec))
-        kernels_ms = tile_ms + (wgrad_ms or 0.0)
-        achieved = f_pt * n / (kernels_ms * 1e-3) / 1e12
-        traffic, traffic_src = hbm_traffic(args.workload, kernel, n)
-        roof = {'bound': 'mfma', 'kernel': kernel, 'achieved': achieved, 'peak': PEAK_FP32_MFMA_TFLOPS, 'unit': 'TFLOP/s',
-                'frac': achieved / PEAK_FP32_MFMA_TFLOPS, 'flops_per_point': f_pt, 'kernel_ms': kernels_ms,
-                'executed': {'streams': s_exec, 'flops_per_point': f_exec,
-                             'tflops': f_exec * n / (kernels_ms * 1e-3) / 1e12,
-                             'frac': f_exec * n / (kernels_ms * 1e-3) / 1e12 / PEAK_FP32_MFMA_TFLOPS},
-                'traffic': traffic,
-                # north_star asks for "HBM GB/s": the fabric-side bytes of the committed PMC passes over this run's kernel time
-                'hbm_gbps': (traffic / (kernels_ms * 1e-3) / 1e9) if traffic else None,
-                'traffic_source': ((f'{traffic_src}: rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of this command, committed, same kernel '
-                                    'sources (content hash); NOT measured in this run') if traffic else traffic_src) if traffic_src else None}
-        if roof_note:
-            roof['what'] = roof_note
-        if kernel_variant(kernel):
-            # split-bf16 kernel: the matrix pipe executes SIX bf16 MFMA flops per fp32-equivalent flop (products a_i b_j, i + j <= 2)
-            # and its bound is the dense bf16 MFMA peak; the fp32-equivalent figures stay alongside (they may exceed the fp32
-            # MFMA peak: that pipe is not the one in use)
-            bf16_tflops = 6.0 * roof['executed']['tflops']
-            roof.update({'fp32_equivalent': {'achieved': achieved, 'frac_of_fp32_mfma_peak': achieved / PEAK_FP32_MFMA_TFLOPS,
-                                             'executed_tflops': roof['executed']['tflops']},
-                         'achieved': bf16_tflops, 'peak': PEAK_BF16_MFMA_TFLOPS, 'frac': bf16_tflops / PEAK_BF16_MFMA_TFLOPS,
-                         'what': 'bf16 MFMA flops executed (6 partial products per fp32-equivalent flop of the S-executed GEMMs) '
-                                 'over the dense bf16 MFMA peak; fp32_equivalent = SURVEY 8d algorithmic figure'})
-        if wgrad_ms:
-            # the weight-gradient GEMMs (a third of the hidden-layer FLOPs) run in their own launch for widths >= 128
-            inner = sum(a * b for a, b in zip(model.layer_dims[1:-1], model.layer_dims[2:]))
-            roof['kernels'] = {
-                kernel: {'ms': tile_ms, 'executed_tflops': (f_exec - 2 * s_exec * inner) * n / (tile_ms * 1e-3) / 1e12},
-                (wgrad_kernel or 'pinn_wgrad_kernel'): {'ms': wgrad_ms, 'executed_tflops': 2 * s_exec * inner * n / (wgrad_ms * 1e-3) / 1e12}}
+        print(f'[bench] gpu: {dt / steps * 1e3:.4f} ms/step by HIP events ({host_dt / steps * 1e3:.4f} by the host clock)'
+              + (f', tile kernel {tile_ms:.4f} ms' if tile_ms is not None else '') + (f', wgrad kernel {wgrad_ms:.4f} ms' if wgrad_ms else ''),
+              file=sys.stderr)
+        roof = None
+        if args.full:
+            # algorithmic FLOPs: the reference's formulation (one stream per derivative D(...) asks for). The
+            # kernels propagate the second derivatives a Laplacian / wave / heat operator needs as ONE combined stream, so the
+            # matrix pipe executes S_exec / S of that figure; both are reported.
+            f_pt = flops_per_point(model.layer_dims, spec.n_streams)
+            plan = solver.residual_plan
+            s_exec = (2 + spec.nd) if (plan is not None and plan.comb_w is not None and not generic) else spec.n_streams
+            f_exec = flops_per_point(model.layer_dims, s_exec)
+            roof_note = None
+            if generic and len(spec.groups) > 1:
+                # direction groups (width 512, many directions): kernel_ms is the LAST backward launch -- one group's streams -- so the FLOPs it is
+                # priced with are that group's too (the whole-step count over one launch's time read 1.09 of the peak on poisson512)
+                s_exec = len(spec.groups[-1][2])
+                f_pt = f_exec = flops_per_point(model.layer_dims, s_exec)
+                roof_note = ('generic path in %d direction groups: kernel_ms, flops_per_point and frac describe the LAST pinn_jet_backward launch '
+                             '(the %d streams of its group); `value` is the whole step' % (len(spec.groups), s_exec))
+            kernels_ms = tile_ms + (wgrad_ms or 0.0)
+            achieved = f_pt * n / (kernels_ms * 1e-3) / 1e12
+            traffic, traffic_src = hbm_traffic(args.workload, kernel, n)
+            roof = {'bound': 'mfma', 'kernel': kernel, 'achieved': achieved, 'peak': PEAK_FP32_MFMA_TFLOPS, 'unit': 'TFLOP/s',
+                    'frac': achieved / PEAK_FP32_MFMA_TFLOPS, 'flops_per_point': f_pt, 'kernel_ms': kernels_ms,
+                    'executed': {'streams': s_exec, 'flops_per_point': f_exec,
+                                 'tflops': f_exec * n / (kernels_ms * 1e-3) / 1e12,
+                                 'frac': f_exec * n / (kernels_ms * 1e-3) / 1e12 / PEAK_FP32_MFMA_TFLOPS},
+                    'traffic': traffic,
+                    # north_star asks for "HBM GB/s": the fabric-side bytes of the committed PMC passes over this run's kernel time
+                    'hbm_gbps': (traffic / (kernels_ms * 1e-3) / 1e9) if traffic else None,
+                    'traffic_source': ((f'{traffic_src}: rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of this command, committed, same kernel '
+                                        'sources (content hash); NOT measured in this run') if traffic else traffic_src) if traffic_src else None}
+            if roof_note:
+                roof['what'] = roof_note
+            if kernel_variant(kernel):
+                # split-bf16 kernel: the matrix pipe executes SIX bf16 MFMA flops per fp32-equivalent flop (products a_i b_j, i + j <= 2)
+                # and its bound is the dense bf16 MFMA peak; the fp32-equivalent figures stay alongside (they may exceed the fp32
+                # MFMA peak: that pipe is not the one in use)
+                bf16_tflops = 6.0 * roof['executed']['tflops']
+                roof.update({'fp32_equivalent': {'achieved': achieved, 'frac_of_fp32_mfma_peak': achieved / PEAK_FP32_MFMA_TFLOPS,
+                                                 'executed_tflops': roof['executed']['tflops']},
+                             'achieved': bf16_tflops, 'peak': PEAK_BF16_MFMA_TFLOPS, 'frac': bf16_tflops / PEAK_BF16_MFMA_TFLOPS,
+                             'what': 'bf16 MFMA flops executed (6 partial products per fp32-equivalent flop of the S-executed GEMMs) '
+                                     'over the dense bf16 MFMA peak; fp32_equivalent = SURVEY 8d algorithmic figure'})
+            if wgrad_ms:
+                # the weight-gradient GEMMs (a third of the hidden-layer FLOPs) run in their own launch for widths >= 128
+                inner = sum(a * b for a, b in zip(model.layer_dims[1:-1], model.layer_dims[2:]))
+                roof['kernels'] = {
+                    kernel: {'ms': tile_ms, 'executed_tflops': (f_exec - 2 * s_exec * inner) * n / (tile_ms * 1e-3) / 1e12},
+                    (wgrad_kernel or 'pinn_wgrad_kernel'): {'ms': wgrad_ms, 'executed_tflops': 2 * s_exec * inner * n / (wgrad_ms * 1e-3) / 1e12}}
         if generic:
             gg = getattr(solver, '_generic_graph', None) or {}
             step_path = ('generic: pinn_jet_forward -> the equation in torch (autograd over its own ops) -> pinn_jet_backward%s -> Adam launch; roofline.kernel_ms covers the backward launch only'
@@ -707,14 +755,21 @@ def main():
             'timing': 'HIP events on the launch stream; host clock %.4f ms/step; `value` / `settled` = steady state: %.2f s of unrelated fp32 GEMM load between the `cold` pass (same W + K steps, taken first) and the warmup steps (clock ramp of a fresh process, --settle)' % (host_dt / steps * 1e3, args.settle),
             'roofline': roof,
         }
+        if not args.full:
+            # (a plain run measures the headline alone: the side figures above are --full's)
+            for key in ('cold', 'strong', 'gemm_bf16x3', 'roofline'):
+                del out[key]
+            out['timing'] = ('HIP events on the launch stream; host clock %.4f ms/step; `value` / `settled` = steady state: %.2f s of unrelated fp32 GEMM '
+                             'load before the warmup steps (clock ramp of a fresh process, --settle)' % (host_dt / steps * 1e3, args.settle))
         if on_cpu:
             out['data'] = 'PLUMBING TEST on the CPU emulator build -- not a measurement'
-        if not args.no_cpu_baseline and world == 1:      # reported at N = 1 only (the other ranks would wait on it)
+        if args.full and not args.no_cpu_baseline and world == 1:      # reported at N = 1 only (the other ranks would wait on it)
             out['cpu_baseline'] = cpu_baseline(args.workload, cpu_batch)
-        out['sustained'] = sustained
-        if (args.workload == 'cfg2' and world == 1 and not on_cpu and not args.no_configs and not args.lib and not args.batch
+        if args.full:
+            out['sustained'] = sustained
+        if (args.full and args.workload == 'cfg2' and world == 1 and not on_cpu and not args.no_configs and not args.lib and not args.batch
                 and not args.global_points and not args.unfused and args.gemm == 'fp32'):
-            # driver time behind ALL five BASELINE configs: compact lines of the other four in the default run
+            # driver time behind ALL five BASELINE configs: compact lines of the other four in a --full run
             out['baseline_configs'] = baseline_configs(device, args.no_parity)
         if parity_at_start is not None:
             out['parity_checked'] = parity_at_start

@@ -1,6 +1,7 @@
 """ TEST INFRASTRUCTURE ONLY -- generates `tests/golden/*.npz` from the UNMODIFIED reference.
 
 Run in the build container (needs /root/reference): `python -m oracle.make_golden`.
+`python -m oracle.make_golden --reference-check` writes the reference's own predict on the cfg1 fixture (`reference_check`).
 For every workload in `pinn_configs.py` it builds the reference `Solver` (pydens/model_torch.py imported by
 path with the batchflow stand-in), records its initial parameters, a fixed stream of point batches, and what
 the reference computes on them: u_hat, residual, loss and parameter gradients on batch 0, then the losses and
@@ -90,5 +91,35 @@ def main():
         print(name, 'loss0', float(blob['loss0']), 'losses', blob['losses'], os.path.getsize(path) // 1024, 'KiB')
 
 
+REFERENCE_CHECK = 'reference_cfg1_predict.npz'
+
+
+def reference_check():
+    """ `python -m oracle.make_golden --reference-check`: what the reference predicts on the cfg1 fixture's parameters and evaluation
+    points, stored apart from the fixture with those inputs (tests/test_oracle_vs_golden.py::test_live_reference_matches_golden holds
+    the fixture to it, so a cfg1.npz that the reference does not reproduce fails without the reference at hand) """
+    ref = load_reference()
+    golden = np.load(os.path.join(ROOT, 'tests', 'golden', 'cfg1.npz'))
+    n = int(golden['n_param_tensors'])
+    params = [golden[f'param_{i}'] for i in range(n)]
+    cfg = pc.make_config('cfg1', ref.D, torch)
+    solver = ref.Solver(cfg['equation'], **cfg['solver_kwargs'])
+    lins = [m for m in solver.model.conv_block if isinstance(m, torch.nn.Linear)]
+    with torch.no_grad():
+        it = iter(params)
+        for lin in lins:
+            lin.weight.copy_(torch.from_numpy(next(it)))
+            lin.bias.copy_(torch.from_numpy(next(it)))
+    pts = golden['points'][1]
+    blob = {f'param_{i}': p for i, p in enumerate(params)}
+    blob.update(n_param_tensors=np.array(n), points=pts, predict=solver.predict(pts[:, 0], pts[:, 1])[:, 0])
+    path = os.path.join(ROOT, 'tests', 'golden', REFERENCE_CHECK)
+    np.savez(path, **blob)
+    print(REFERENCE_CHECK, os.path.getsize(path) // 1024, 'KiB')
+
+
 if __name__ == '__main__':
-    main()
+    if sys.argv[1:] == ['--reference-check']:
+        reference_check()
+    else:
+        main()

@@ -2,7 +2,7 @@
 
 `/root/reference/pydens/model_torch.py` needs `batchflow.models.torch.Block` (model_torch.py:12), which is not
 vendored; `oracle/batchflow_shim` provides the stand-in. /root/reference does not exist on the GPU box, so this
-loader is only used by `oracle/make_golden.py` and by CPU tests that skip when the reference is absent.
+loader is only used by `oracle/make_golden.py` (the tests read what it wrote under `tests/golden/`).
 """
 import importlib.util
 import os

@@ -5,7 +5,7 @@ for w in $WL; do
   for rep in 1 2; do
     for lib in "$@" product; do
       L=""; [ $lib != product ] && L="--lib $lib"
-      timeout 300 python bench.py --workload $w --no-cpu-baseline --no-strong --no-side $L > $OUT/bench_${w}_$(basename $lib .so)_$rep.txt 2> $OUT/bench_${w}_$(basename $lib .so)_$rep.err
+      timeout 300 python bench.py --full --workload $w --no-cpu-baseline --no-strong --no-side $L > $OUT/bench_${w}_$(basename $lib .so)_$rep.txt 2> $OUT/bench_${w}_$(basename $lib .so)_$rep.err
       echo "$w $(basename $lib .so) #$rep: $(grep 'bench\] gpu' $OUT/bench_${w}_$(basename $lib .so)_$rep.err)"
     done
   done

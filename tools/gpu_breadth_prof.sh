@@ -9,7 +9,7 @@ for w in "$@"; do
   cp $OUT/prof_$w/kernel_stats.csv $OUT/kernel_stats_$w.csv 2>/dev/null
 done
 for w in "$@"; do
-  timeout 300 python bench.py --workload $w --no-cpu-baseline --no-strong > $OUT/bench_$w.txt 2> $OUT/bench_$w.err
+  timeout 300 python bench.py --full --workload $w --no-cpu-baseline --no-strong > $OUT/bench_$w.txt 2> $OUT/bench_$w.err
   echo "$w: $(grep 'bench\] gpu' $OUT/bench_$w.err) traffic $(python -c "import json; print(json.loads(open('$OUT/bench_$w.txt').read().strip().splitlines()[-1])['roofline'].get('traffic'))" 2>/dev/null)"
   cp profiles/r04_${w}_pmc.json $OUT/pmc_$w.json 2>/dev/null
 done
