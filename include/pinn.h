@@ -172,7 +172,32 @@ typedef struct pinn_residual {
      * d(loss)/d(b_L) came out 1.1 - 1.4e-5 from the fp64 oracle for that reason alone (the fp32 reference: 0.5 - 1e-5, same cause;
      * tools/cfg4_bl_probe.py). The pre-pass is a handful of operations per point, once per step. */
     double pre_consts64[PINN_MAX_CONSTS];
+    /* Criterion of the fused step: what `criterion(equation(u_hat, *xs), 0)` (model_torch.py:396-410, :448, :457) makes of the residual r of a
+     * point -- loss = scale * sum rho(r), upstream gradient scale * rho'(r) -- for the pointwise torch criteria with a closed form against a
+     * zero target (PINN_CRIT_* below). All three fields zero = nn.MSELoss(reduction='mean'): a caller that zero-initialises the struct sees
+     * the arithmetic the library had before these fields existed, bit for bit.
+     *   criterion   PINN_CRIT_MSE / _L1 / _SMOOTH_L1 / _HUBER; anything else is refused
+     *   crit_param  beta of nn.SmoothL1Loss (>= 0; 0 is L1, as in torch), delta of nn.HuberLoss (> 0, else refused); ignored by MSE / L1
+     *   crit_sum    != 0: reduction='sum'. The entry points that derive the scale from n_points themselves (pinn_residual_adam_step,
+     *               pinn_fit_steps, pinn_fit_steps_graph) then use 1 instead of 1 / n_points; pinn_residual_step / _step_add take the scale
+     *               from their caller in either case (`inv_n_global`: 1 for a sum, 1 / world for a term every data-parallel rank evaluates).
+     * Non-MSE criteria run on the general tile kernels and on the residual-program kernels; the shape-specialised affine instantiations are
+     * compiled for MSE alone, and a call with another criterion takes the general kernel of the same stream shape. */
+    int criterion;
+    float crit_param;
+    int crit_sum;
 } pinn_residual_t;
+
+/* rho(r) and rho'(r) of pinn_residual_t::criterion:
+ *   PINN_CRIT_MSE        nn.MSELoss              r^2                                                  2 r
+ *   PINN_CRIT_L1         nn.L1Loss               |r|                                                  sign(r), sign(0) = 0 (torch's abs backward)
+ *   PINN_CRIT_SMOOTH_L1  nn.SmoothL1Loss(beta)   |r| < beta: r^2 / (2 beta), else |r| - beta / 2      r / beta or sign(r)
+ *   PINN_CRIT_HUBER      nn.HuberLoss(delta)     |r| <= delta: r^2 / 2, else delta (|r| - delta / 2)  r or delta sign(r) */
+#define PINN_CRIT_MSE       0
+#define PINN_CRIT_L1        1
+#define PINN_CRIT_SMOOTH_L1 2
+#define PINN_CRIT_HUBER     3
+#define PINN_CRIT_LAST      3
 
 /* Descriptor of network + ansatz.  Replaces ConvBlockModel.__init__/TorchModel.__init__ bookkeeping
  * (model_torch.py:19-50, :158-168).  layer_dims[0] = ndims+nparams, layer_dims[n_layers] = 1.
@@ -232,7 +257,7 @@ int pinn_jet_backward(pinn_t* net, const float* params, const float* xs, int64_t
                       const float* grad_streams, float* grads, int accumulate, void* workspace, size_t workspace_bytes,
                       void* stream);
 
-/* One fused residual + gradient evaluation: forward jets, ansatz, residual program, mean-square loss and the
+/* One fused residual + gradient evaluation: forward jets, ansatz, residual program, mean-square loss (or residual->criterion) and the
  * full reverse sweep, in one launch (the x-only pre-pass runs in its prologue) + a reduction launch.  Replaces model_torch.py:437-460
  * (forward, equation, MSELoss vs zeros, backward).  grads[0..p_core) receives d(loss)/dparams with
  * loss = inv_n_global * sum r^2 over THIS call's points (data-parallel ranks pass 1/N_global and all-reduce

@@ -1009,6 +1009,14 @@ static int residual_step_impl(pinn_t* net, const pinn_residual_t* residual, cons
     }
     a.mode = PINN_MODE_STEP;
     a.inv_n = inv_n_global;
+    // criterion of the step (include/pinn.h PINN_CRIT_*; all zero: mean-square)
+    if (residual->criterion < PINN_CRIT_MSE || residual->criterion > PINN_CRIT_LAST) return fail("unknown criterion code %d", residual->criterion);
+    if (residual->criterion == PINN_CRIT_HUBER && !(residual->crit_param > 0.0f)) return fail("HuberLoss needs delta > 0 (crit_param=%g)", (double)residual->crit_param);
+    if (residual->criterion == PINN_CRIT_SMOOTH_L1 && !(residual->crit_param >= 0.0f)) return fail("SmoothL1Loss needs beta >= 0 (crit_param=%g)", (double)residual->crit_param);
+    a.crit = residual->criterion;
+    a.crit_param = residual->crit_param;
+    if (a.crit == PINN_CRIT_SMOOTH_L1 && a.crit_param == 0.0f) a.crit = PINN_CRIT_L1;      // (as torch: smooth_l1_loss with beta 0 is l1_loss)
+    if (a.crit == PINN_CRIT_MSE || a.crit == PINN_CRIT_L1) a.crit_param = 0.0f;
     if (make_plan(net, n_points, nd, n2, &plan, PINN_MODE_STEP, residual->kind, comb, &a)) return 1;      // with the call's own arguments
     return run_train(net, &a, plan, nd, grads, accumulate, workspace, workspace_bytes, stream, &residual->pre, adam, residual->pre_consts64);
 }
@@ -1035,8 +1043,9 @@ int pinn_residual_adam_step(pinn_t* net, const pinn_residual_t* residual, float*
     if (!net || !exp_avg || !exp_avg_sq || !step_ptr) return fail("null argument");
     if (step < 1) return fail("step must be >= 1");
     AdamArgs adam = {params, exp_avg, exp_avg_sq, mask, step_ptr, step, lr, beta1, beta2, eps, loss_out, net->lay.off_loss};
+    // (reduction='sum', pinn_residual_t::crit_sum: no division by the number of points)
     return residual_step_impl(net, residual, params, xs, n_points, dir_cols, nd, n2, ic_streams, ic_const,
-                              1.0f / (float)n_points, grads, workspace, workspace_bytes, stream, &adam);
+                              (residual && residual->crit_sum) ? 1.0f : 1.0f / (float)n_points, grads, workspace, workspace_bytes, stream, &adam);
 }
 
 // the sampler description of a fit chunk in the form the reduction's tail takes (non-zero: columns it cannot draw)
@@ -1169,7 +1178,10 @@ int pinn_fit_steps_graph(pinn_t* net, const pinn_residual_t* residual, float* pa
     const long long ints[] = {(long long)n_points, nd, n2, (long long)workspace_bytes, net->gemm_mode, net->tanh_mode, net->max_per_cu,
                               net->prepass_in_kernel, (long long)net->wgx_chunk_bytes};
     key_mix(key, ints, sizeof(ints));
-    const float flts[] = {ic_const, lr, beta1, beta2, eps};
+    const float flts[] = {ic_const, lr, beta1, beta2, eps, residual->crit_param};
+    // (the criterion is part of `residual`, hashed above; named here once more so that the key does not depend on where the fields sit)
+    const int crit_key[] = {residual->criterion, residual->crit_sum};
+    key_mix(key, crit_key, sizeof(crit_key));
     key_mix(key, flts, sizeof(flts));
     key_mix(key, kind, sizeof(int) * net->lay.d); key_mix(key, a, sizeof(float) * net->lay.d); key_mix(key, b, sizeof(float) * net->lay.d);
     key_mix(key, dir_cols, sizeof(int) * (nd > 0 ? nd : 0));

@@ -549,6 +549,9 @@ constexpr int WGXH = PINN_HEAVY_WGX ? WGXV : 0;
 // (program = true, round 6: the same shapes with a residual PROGRAM -- PinnShape SPEC | 4; the coefficient rows belong to the affine form)
 static int pinn_spec_of(const PinnKArgs* a, int nd, int n2, bool program = false) {
     if (a->mode != PINN_MODE_STEP || a->res_kind != (program ? PINN_RES_PROGRAM : PINN_RES_AFFINE) || a->s_user != 1 + nd + n2 || a->ic_var1 > 0) return 0;
+    // (the shape-specialised AFFINE kernels are compiled for the mean-square criterion alone -- PinnShape::crit; their residual-program twins
+    //  read the criterion from the arguments)
+    if (!program && a->crit != PINN_CRIT_MSE) return 0;
     for (int k = 0; k < nd; ++k)
         if (a->dir_cols[k] != k) return 0;
     for (int s = 0; s < a->s_user && !program; ++s)

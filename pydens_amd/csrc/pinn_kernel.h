@@ -139,6 +139,8 @@ struct PinnKArgs {
     pinn_program_t pre;          // n_ops > 0: the tile kernel evaluates the pre-pass itself for the points of its own tiles
                                  // (kernel prologue) instead of a separate launch in front of it
     PinnPreConsts pre_consts64;  // ... in fp64, with these constants (round 6)
+    int crit;                    // PINN_CRIT_* (pinn_residual_t::criterion): read by the point stage of the general and the residual-program
+    float crit_param;            // kernels only (PinnShape::crit); SmoothL1 beta / Huber delta. `inv_n` already is 1 for reduction='sum'
 };
 
 template <int HP_, int ND_, int N2_, int MT_ = 1, bool SPLIT_ = false>
@@ -857,7 +859,28 @@ struct PinnShape {
     static PINN_DEVICE int res_kind(const PinnKArgs& A) { return FIXED ? (PROGRAM ? (int)PINN_RES_PROGRAM : (int)PINN_RES_AFFINE) : A.res_kind; }
     static PINN_DEVICE int s_user(const PinnKArgs& A) { return FIXED ? 99 : A.s_user; }
     static PINN_DEVICE int coef_row(const PinnKArgs& A, int s) { return FIXED ? -1 : A.coef_row[s]; }
+    // criterion of the step: a compile-time fact (MSE) in the shape-specialised AFFINE kernels -- the BASELINE kernels are bound by the
+    // instructions they issue and carry nothing for it; the launcher sends other criteria to the general kernel (pinn_spec_of) --,
+    // a wave-uniform kernel argument in the general and the residual-program kernels
+    static PINN_DEVICE int crit(const PinnKArgs& A) { return (FIXED && !PROGRAM) ? (int)PINN_CRIT_MSE : A.crit; }
 };
+
+// rho(r) and rho'(r) of the closed-form criteria other than MSE (include/pinn.h PINN_CRIT_*), both times `scale`: what torch's
+// l1_loss / smooth_l1_loss / huber_loss against a zero target and their backward compute per element
+PINN_DEVICE inline void pinn_criterion(int crit, float par, float r, float scale, float& loss, float& w) {
+    const float a = fabsf(r);
+    const float sgn = r > 0.0f ? 1.0f : (r < 0.0f ? -1.0f : 0.0f);
+    float rho = a, drho = sgn;                                          // PINN_CRIT_L1
+    if (crit == PINN_CRIT_SMOOTH_L1) {
+        if (a < par) { rho = 0.5f * r * r / par; drho = r / par; }
+        else rho = a - 0.5f * par;
+    } else if (crit == PINN_CRIT_HUBER) {
+        if (a <= par) { rho = 0.5f * r * r; drho = r; }
+        else { rho = par * (a - 0.5f * par); drho = par * sgn; }
+    }
+    loss = rho * scale;
+    w = drho * scale;
+}
 
 template <int ND, int N2P>
 struct PinnPointPre {
@@ -1120,10 +1143,11 @@ PINN_DEVICE void pinn_point_stage(const PinnKArgs& A, const float* params_, cons
         float r = pre.src;
 #pragma unroll
         for (int s = 0; s < S; ++s) r = fmaf(pre.cs[s], u[s], r);
-        const float w = valid ? 2.0f * r * A.inv_n : 0.0f;
+        float w = valid ? 2.0f * r * A.inv_n : 0.0f;
+        out.loss = valid ? r * r * A.inv_n : 0.0f;
+        if (SH::crit(A) != PINN_CRIT_MSE && valid) pinn_criterion(SH::crit(A), A.crit_param, r, A.inv_n, out.loss, w);
 #pragma unroll
         for (int s = 0; s < S; ++s) gu[s] = w * pre.cs[s];
-        out.loss = valid ? r * r * A.inv_n : 0.0f;
     } else if (WITH_PROGRAMS && SH::mode(A) == PINN_MODE_STEP) {
         // registers: S streams (the INSTANTIATION's S), d input columns, n_aux pre-pass rows (already staged by
         // pinn_point_prefetch), then temporaries
@@ -1135,12 +1159,13 @@ PINN_DEVICE void pinn_point_stage(const PinnKArgs& A, const float* params_, cons
         const int vbase = S + SH::d(A) + A.n_aux;
         for (int k = 0; k < A.n_vars; ++k) pregs[(vbase + k) * T] = params_[A.off_extra + k];
         const float r = pinn_prog_forward(A.prog, pregs, T);
-        const float w = valid ? 2.0f * r * A.inv_n : 0.0f;
+        float w = valid ? 2.0f * r * A.inv_n : 0.0f;
+        out.loss = valid ? r * r * A.inv_n : 0.0f;
+        if (SH::crit(A) != PINN_CRIT_MSE && valid) pinn_criterion(SH::crit(A), A.crit_param, r, A.inv_n, out.loss, w);
         pinn_prog_backward(A.prog, pregs, padj, T, w);          // seeded with d(loss)/dr: adjoints come out scaled
 #pragma unroll
         for (int s = 0; s < S; ++s) { gu[s] = padj[s * T]; padj[s * T] = 0.0f; }
         for (int c = 0; c < SH::d(A) + A.n_aux; ++c) padj[(S + c) * T] = 0.0f;
-        out.loss = valid ? r * r * A.inv_n : 0.0f;
     } else {
         if (valid) {
 #pragma unroll

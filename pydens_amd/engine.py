@@ -18,6 +18,7 @@ MAX_OPS, MAX_CONSTS, MAX_REGS = 64, 32, 40
 MAX_STREAMS, MAX_AUX, MAX_VARS = 7, 8, 8
 SAMPLE_UNIFORM, SAMPLE_NORMAL, SAMPLE_CONST = 0, 1, 2
 RES_PROGRAM, RES_AFFINE = 0, 1
+CRIT_MSE, CRIT_L1, CRIT_SMOOTH_L1, CRIT_HUBER = 0, 1, 2, 3      # include/pinn.h PINN_CRIT_*
 SKIP_PRE = 0x100         # include/pinn.h PINN_SKIP_PRE
 ACT_CODES = {'tanh': 0, 'sigmoid': 1, 'sin': 2, 'identity': 3, 'softplus': 4, 'silu': 5, 'swish': 5, 'gelu': 6,
              # round 5 (include/pinn.h PINN_ACT_RELU ..): torch-default forms
@@ -58,7 +59,14 @@ class Residual(ctypes.Structure):
                 ('src_const', ctypes.c_float), ('src_row', ctypes.c_int),
                 ('combined', ctypes.c_int), ('comb_w', ctypes.c_float * MAX_DIRS), ('n_vars', ctypes.c_int),
                 ('ic_var1', ctypes.c_int), ('ic_rows', ctypes.c_int), ('ic_row', ctypes.c_int * MAX_STREAMS),
-                ('ic_cst', ctypes.c_float * MAX_STREAMS), ('pre_consts64', ctypes.c_double * MAX_CONSTS)]
+                ('ic_cst', ctypes.c_float * MAX_STREAMS), ('pre_consts64', ctypes.c_double * MAX_CONSTS),
+                # criterion of the fused step (all zero: MSELoss, reduction 'mean')
+                ('criterion', ctypes.c_int), ('crit_param', ctypes.c_float), ('crit_sum', ctypes.c_int)]
+
+    def set_criterion(self, code=CRIT_MSE, param=0.0, reduce_sum=False):
+        """ pointwise criterion against a zero target: CRIT_* code, its one parameter (SmoothL1 beta / Huber delta), reduction 'sum' """
+        self.criterion, self.crit_param, self.crit_sum = int(code), float(param), 1 if reduce_sum else 0
+        return self
 
     @classmethod
     def build(cls, kind, n_aux, pre, program=None, coef=(), coef_row=(), src_const=0.0, src_row=-1, comb_w=None, n_vars=0,

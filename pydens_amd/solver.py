@@ -163,6 +163,11 @@ class Solver:
         self._losses = []
         self._pending = []
         self.use_fused = True       # diagnostic switch: False keeps every fit on the generic step path
+        self.criterion_path = 'generic'     # set_criterion_path: closed-form criteria other than MSELoss() on the fused step or not
+        self._crit_sum = False              # reduction='sum' in the fused steps of the running fit
+        self.last_fit_criterion = None
+        if os.environ.get('PYDENS_AMD_CRITERION'):
+            self.set_criterion_path(os.environ['PYDENS_AMD_CRITERION'])
         self.optimizer = None
 
         self.model = model(**kwargs, ndims=ndims, initial_condition=initial_condition,
@@ -214,6 +219,55 @@ class Solver:
         operand as three bf16, six partial products, fp32 accumulate -- the split-bf16 kernels where they are built, the fp32
         kernels elsewhere; include/pinn.h pinn_set_gemm_mode). Also settable for a whole process with PYDENS_AMD_GEMM. """
         self.model.net.set_gemm_mode(mode)
+
+    CRITERION_PATHS = ('generic', 'fused')
+
+    def set_criterion_path(self, path):
+        """ where `fit(criterion=...)` other than `nn.MSELoss()` runs: 'generic' (default: the criterion module is called on the residual
+        as torch code, between pinn_jet_forward and pinn_jet_backward) or 'fused' -- nn.L1Loss, nn.SmoothL1Loss, nn.HuberLoss and
+        nn.MSELoss with reduction 'mean' or 'sum' are evaluated in closed form inside the point stage of the fused step (include/pinn.h
+        PINN_CRIT_*), for the equation term and every lowered constraint term; everything else (other modules, subclasses, callables,
+        reduction='none') keeps the generic path in either setting. Process-wide: PYDENS_AMD_CRITERION. """
+        if path not in self.CRITERION_PATHS:
+            raise ValueError(f'criterion path {path!r}: expected one of {sorted(self.CRITERION_PATHS)}')
+        self.criterion_path = path
+
+    def _lower_criterion(self, criterion):
+        """ (code, parameter, sum) of a criterion the point stage has in closed form, else None. By EXACT type: a subclass may override
+        forward(). `nn.MSELoss(reduction='mean')` is always lowerable (the fused step's own loss); the others only on the 'fused'
+        criterion path. """
+        reduction = getattr(criterion, 'reduction', None)
+        if reduction not in ('mean', 'sum'):
+            return None
+        if isinstance(criterion, nn.MSELoss) and reduction == 'mean':      # (as before this switch existed: subclasses included)
+            return (engine.CRIT_MSE, 0.0, False)
+        if self.criterion_path != 'fused':
+            return None
+        kind = type(criterion)
+        if kind is nn.MSELoss:
+            return (engine.CRIT_MSE, 0.0, reduction == 'sum')
+        if kind is nn.L1Loss:
+            return (engine.CRIT_L1, 0.0, reduction == 'sum')
+        if kind is nn.SmoothL1Loss:
+            beta = float(criterion.beta)
+            if beta < 0.0:
+                return None
+            # (beta = 0 is L1, as in torch)
+            return (engine.CRIT_SMOOTH_L1, beta, reduction == 'sum') if beta > 0.0 else (engine.CRIT_L1, 0.0, reduction == 'sum')
+        if kind is nn.HuberLoss:
+            delta = float(criterion.delta)
+            return (engine.CRIT_HUBER, delta, reduction == 'sum') if delta > 0.0 else None
+        return None
+
+    def _apply_criterion(self, lowered, nums_constraints):
+        """ write the criterion of this fit call into the residual structs its fused steps hand to the library """
+        code, param, reduce_sum = lowered
+        self._crit_sum = reduce_sum
+        if self.program is not None:
+            self.program.set_criterion(code, param, reduce_sum)
+        for num in nums_constraints:
+            if num < len(self.constraint_plans) and self.constraint_plans[num] is not None:
+                self.constraint_plans[num]['program'].set_criterion(code, param, reduce_sum)
 
     def set_tanh_mode(self, mode):
         """ 'fast' (default) or 'accurate': tanh of small arguments by a minimax polynomial in the kernels that have that form (the
@@ -518,10 +572,10 @@ class Solver:
         return residual
 
     def _constraint_step(self, num, world, accumulate):
-        """ gradient + loss of constraint term `num` (mean of its squared values, reference :457), added to / stored in
-        `self.grads`; every data-parallel rank evaluates it, hence the 1 / world in front of the all-reduce. """
+        """ gradient + loss of constraint term `num` (the fit's criterion on its values, reference :457: their mean square by default),
+        added to / stored in `self.grads`; every data-parallel rank evaluates it, hence the 1 / world in front of the all-reduce. """
         cp, model = self.constraint_plans[num], self.model
-        n_c = cp['points'].shape[0]
+        n_c = 1 if self._crit_sum else cp['points'].shape[0]            # (reduction='sum': no division by the number of points)
         model.net.residual_step(cp['program'], model.flat, cp['points'], self.grads, model.workspace(n_c, 0, 0), (), 0,
                                 ic_streams=cp['ic'], ic_const=model.kernel_ic_const(),
                                 inv_n_global=1.0 / (n_c * world), accumulate=accumulate)
@@ -853,11 +907,11 @@ class Solver:
         else:
             self.optimizer.refresh()
         self._constraints_seen |= {num for num in nums_constraints if num < len(self.constraints)}
-        mse_mean = isinstance(criterion, nn.MSELoss) and criterion.reduction == 'mean'
+        crit = self._lower_criterion(criterion)          # None: not lowerable (generic path)
         lowered = all(num < len(self.constraint_plans) and self.constraint_plans[num] is not None
                       for num in nums_constraints)
         only_known_terms = all(term == 'equation' or 'constraint' in term for term in loss_terms)
-        fused = (self.use_fused and mse_mean and not self.ic_trainable and only_known_terms and lowered
+        fused = (self.use_fused and crit is not None and not self.ic_trainable and only_known_terms and lowered
                  and len(loss_terms) > 0 and (self.program is not None or 'equation' not in loss_terms))
         rank, world = self._world()
         if world > 1:
@@ -875,6 +929,8 @@ class Solver:
         done = [0]
         self._pending.append((history, done))       # registered up front: an interrupted fit keeps the losses it reached
         self.last_fit_path = 'fused' if fused else 'generic'
+        self.last_fit_criterion = f'{type(criterion).__name__}/{self.last_fit_path}'
+        self._apply_criterion(crit if fused else (engine.CRIT_MSE, 0.0, False), nums_constraints)
         flat_adam = isinstance(self.optimizer, FlatAdam)
         one_launch = fused and world == 1 and flat_adam and tuple(loss_terms) == ('equation',)
         stream = engine.stream_of(model.flat)           # looked up once per call, not per iteration
@@ -1007,7 +1063,7 @@ class Solver:
         n_global = self._global_batch if (world > 1 and getattr(self, '_global_batch', None)) else xs.shape[0] * world
         model.net.residual_step(self.program, model.flat, xs, self.grads, ws, spec.dir_cols, n2,
                                 ic_streams=ic_streams, ic_const=model.kernel_ic_const(),
-                                inv_n_global=1.0 / n_global, stream=stream)
+                                inv_n_global=1.0 if self._crit_sum else 1.0 / n_global, stream=stream)
 
     GENERIC_GRAPH_WARMUP = 3    # eager steps in front of the recording (instantiations, workspaces, autograd buffers settle)
     GENERIC_GRAPH_MIN_REPLAYS = 48      # a recording (device synchronise, gc, allocator trim inside torch.cuda.graph) is only made when at

@@ -1,4 +1,6 @@
-""" Solver.fit rate of ONE BASELINE config (python tools/fit_one.py cfg3 [iters]); rocprofv3-friendly. """
+""" Solver.fit rate of ONE BASELINE config (python tools/fit_one.py cfg3 [iters [criterion [criterion path]]]); rocprofv3-friendly.
+criterion: name of a torch.nn loss module built with its defaults (MSELoss, L1Loss, SmoothL1Loss, HuberLoss); criterion path: 'generic' or
+'fused' (Solver.set_criterion_path). """
 import os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -8,6 +10,8 @@ import pydens_amd as pa
 
 name = sys.argv[1] if len(sys.argv) > 1 else 'cfg3'
 iters = int(sys.argv[2]) if len(sys.argv) > 2 else 30
+crit_name = sys.argv[3] if len(sys.argv) > 3 else 'MSELoss'
+crit_path = sys.argv[4] if len(sys.argv) > 4 else 'generic'
 n = {'cfg1': 100, 'cfg2': 65536, 'cfg3': 262144, 'cfg4': 131072, 'cfg5': 131072}[name]
 torch.manual_seed(0)
 cfg = pc.make_config(name, pa.D, torch)
@@ -17,17 +21,19 @@ import gc
 gc.collect()            # (in front of the warm-up: the collection itself leaves the GPU idle for 40 ms, which costs the clocks)
 gc.freeze()
 gc.disable()
-solver.fit(niters=20, batch_size=n, sampler=sampler)
+solver.set_criterion_path(crit_path)
+criterion = getattr(torch.nn, crit_name)()
+solver.fit(niters=20, batch_size=n, sampler=sampler, criterion=criterion)
 torch.cuda.synchronize()
 # (as `timeit` does: a full collection of Python's cyclic garbage collector stops the launching thread for ~40 ms in a process with torch loaded;
 #  whether one falls into the 64 ms this call of BASELINE config 4 takes depended on the allocation count of the host code -- round 6)
 t0 = time.perf_counter()
-solver.fit(niters=iters, batch_size=n, sampler=sampler)
+solver.fit(niters=iters, batch_size=n, sampler=sampler, criterion=criterion)
 torch.cuda.synchronize()
 dt = time.perf_counter() - t0
 gc.enable()
 losses = solver.losses
-print(f'{name}: Solver.fit {iters / dt:9.1f} it/s  {n * iters / dt:12.4g} points/s  ({dt / iters * 1e3:.3f} ms/it, batch {n}, path {solver.last_fit_path}, '
+print(f'{name}: Solver.fit {iters / dt:9.1f} it/s  {n * iters / dt:12.4g} points/s  ({dt / iters * 1e3:.3f} ms/it, batch {n}, path {solver.last_fit_path}, criterion {solver.last_fit_criterion}, '
       f'loss {float(losses[20]):.4g} -> {float(losses[-1]):.4g})')
 import ctypes
 st = (ctypes.c_int32 * 4)()
