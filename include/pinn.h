@@ -300,6 +300,59 @@ int pinn_adam_step_at(float* params, const float* grads, float* exp_avg, float* 
                       int64_t n, int32_t* step_ptr, int32_t step, float lr, float beta1, float beta2, float eps,
                       float* loss_out, int32_t off_loss, void* stream);
 
+/* The update rule of the optimizer entry points below: the `_single_tensor_*` arithmetic of torch.optim.{Adam, AdamW, SGD, RMSprop}
+ * (the optimizer `Solver.fit(optimizer=...)` names, model_torch.py:420-422, :461) on the flat buffer. At most TWO state arrays per rule, the
+ * `exp_avg` / `exp_avg_sq` arguments of the entry points:
+ *   rule               torch call                                              exp_avg holds        exp_avg_sq holds
+ *   PINN_OPT_ADAM      Adam(lr, betas, eps, weight_decay)                      exp_avg              exp_avg_sq
+ *   PINN_OPT_ADAMW     AdamW(lr, betas, eps, weight_decay)                     exp_avg              exp_avg_sq
+ *   PINN_OPT_SGD       SGD(lr, momentum, dampening, nesterov, weight_decay)    momentum_buffer      (untouched)
+ *   PINN_OPT_RMSPROP   RMSprop(lr, alpha, eps, weight_decay, momentum,         momentum_buffer or   square_avg
+ *                              centered)                                       grad_avg
+ * Adam: weight_decay != 0 adds weight_decay * p to the gradient in front; weight_decay == 0 is the arithmetic of pinn_adam_step, bit for bit.
+ * AdamW: p *= 1 - lr * weight_decay in front of the Adam step (decoupled). SGD: the update of step 1 SETS the momentum buffer to the gradient
+ * (no 1 - dampening), as torch does for a parameter without a buffer; nesterov needs momentum > 0 and dampening == 0 (torch's own check).
+ * RMSprop: momentum > 0 together with centered would need three arrays and is refused. An entry with mask[i] == 0 keeps value AND state: it
+ * is not decayed either. A struct with `rule` and the fields behind `eps` zero and Adam's four numbers filled is plain Adam. Refused (non-zero,
+ * pinn_last_error, nothing launched): an unknown rule, negative lr / eps / weight_decay / momentum / alpha, betas outside [0, 1), the
+ * combinations named above. */
+#define PINN_OPT_ADAM    0
+#define PINN_OPT_ADAMW   1
+#define PINN_OPT_SGD     2
+#define PINN_OPT_RMSPROP 3
+#define PINN_OPT_LAST    3
+typedef struct pinn_optim {
+    int rule;
+    float lr, beta1, beta2, eps, weight_decay, momentum, dampening, alpha;
+    int nesterov, centered;
+} pinn_optim_t;
+
+/* pinn_adam_step / pinn_adam_step_at with the rule of `opt`: step <= 0 counts on the device (step_ptr[0] is incremented and read), step >= 1
+ * is the host's 1-based count (mirrored to step_ptr[0]; loss_out / off_loss as in pinn_adam_step_at). The step count is the optimizer's: SGD
+ * takes "step 1" for "no momentum buffer yet". */
+int pinn_optim_step(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, const uint8_t* mask, int64_t n,
+                    int32_t* step_ptr, const pinn_optim_t* opt, void* stream);
+int pinn_optim_step_at(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, const uint8_t* mask, int64_t n,
+                       int32_t* step_ptr, int32_t step, const pinn_optim_t* opt, float* loss_out, int32_t off_loss, void* stream);
+/* pinn_residual_adam_step, pinn_fit_steps and pinn_fit_steps_graph with the rule of `opt` (the Adam entry points are these with a plain-Adam
+ * struct). The launch-graph cache of pinn_fit_steps_optim_graph keys on the whole struct. */
+int pinn_residual_optim_step(pinn_t* net, const pinn_residual_t* residual, float* params, const float* xs,
+                             int64_t n_points, const int* dir_cols, int nd, int n2, const float* ic_streams,
+                             float ic_const, float* grads, float* exp_avg, float* exp_avg_sq, const uint8_t* mask,
+                             int32_t* step_ptr, int32_t step, const pinn_optim_t* opt, float* loss_out, void* workspace,
+                             size_t workspace_bytes, void* stream);
+int pinn_fit_steps_optim(pinn_t* net, const pinn_residual_t* residual, float* params, float* xs, int64_t n_points,
+                         const int* kind, const float* a, const float* b, uint64_t seed, uint64_t call_index0,
+                         const int* dir_cols, int nd, int n2, float ic_const, float* grads, float* exp_avg, float* exp_avg_sq,
+                         const uint8_t* mask, int32_t* step_ptr, int32_t step0, const pinn_optim_t* opt,
+                         float* loss_history, int32_t k_steps, void* workspace, size_t workspace_bytes, void* stream);
+int pinn_fit_steps_optim_graph(pinn_t* net, const pinn_residual_t* residual, float* params, float* xs, int64_t n_points,
+                               const int* kind, const float* a, const float* b, uint64_t seed, uint64_t call_index0,
+                               const int* dir_cols, int nd, int n2, float ic_const, float* grads, float* exp_avg, float* exp_avg_sq,
+                               const uint8_t* mask, int32_t* step_ptr, int32_t step0, const pinn_optim_t* opt,
+                               float* loss_history, int32_t k_steps, void* workspace, size_t workspace_bytes, void* ctrl,
+                               size_t ctrl_bytes, void* stream);
+
 /* The reference's fit loop (model_torch.py:426-464) for the common case -- on-device column sampler, one equation term on the
  * fused path, Adam -- as ONE call that enqueues `k_steps` iterations: iteration k draws batch `call_index0 + k` into `xs`
  * (pinn_sample_points with kind / a / b / seed), runs pinn_residual_adam_step with Adam step `step0 + k` and leaves the

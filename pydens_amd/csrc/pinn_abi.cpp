@@ -6,6 +6,7 @@
 
 #include <cstdarg>
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <new>
 
@@ -324,32 +325,93 @@ int check_dirs(const pinn_net* net, const int* dir_cols, int nd, int n2p) {
     return 0;
 }
 
+// the update that rides in a step's last reduction launch (or in the one-launch fit chunk): buffers, step, rule
 struct AdamArgs {
     float* params; float* m; float* v; const unsigned char* mask; int* step_ptr;
-    int step_value; float lr, b1, b2, eps;
+    int step_value; PinnOptK opt;
     float* loss_out; int off_loss;
 };
+
+// the decimal a float was most likely written as, as a double: the shortest one that rounds back to it. torch derives 1 - alpha,
+// 1 - dampening and 1 - lr * weight_decay from the caller's Python DOUBLES; pinn_optim_t carries floats, and 1 - (double)0.99f is 1e-6
+// (relative) off 1 - 0.99
+static double widen(float x) {
+    char buf[40];
+    for (int digits = 1; digits <= 9; ++digits) {
+        snprintf(buf, sizeof(buf), "%.*g", digits, (double)x);
+        const double d = strtod(buf, nullptr);
+        if ((float)d == x) return d;
+    }
+    return (double)x;
+}
+
+static PinnOptK plain_adam(float lr, float b1, float b2, float eps) {
+    PinnOptK k;
+    memset(&k, 0, sizeof(k));
+    k.rule = PINN_OPT_ADAM; k.lr = lr; k.b1 = b1; k.b2 = b2; k.eps = eps;
+    k.decay = 1.0f; k.undamp = 1.0f; k.one_m_alpha = 1.0f;
+    return k;
+}
+
+// pinn_optim_t (include/pinn.h) -> what the kernels take; non-zero (pinn_last_error set) for what the library refuses
+static int optim_prepare(const pinn_optim_t* o, PinnOptK* k) {
+    if (!o) return fail("null optimizer description");
+    if (o->rule < 0 || o->rule > PINN_OPT_LAST) return fail("unknown optimizer rule %d", o->rule);
+    if (!(o->lr >= 0.0f)) return fail("optimizer: invalid learning rate %g", (double)o->lr);
+    if (!(o->weight_decay >= 0.0f)) return fail("optimizer: invalid weight_decay value %g", (double)o->weight_decay);
+    *k = plain_adam(o->lr, 0.0f, 0.0f, 0.0f);
+    k->rule = o->rule;
+    k->wd = o->weight_decay;
+    if (o->rule == PINN_OPT_ADAM || o->rule == PINN_OPT_ADAMW) {
+        if (!(o->eps >= 0.0f)) return fail("optimizer: invalid epsilon value %g", (double)o->eps);
+        if (!(o->beta1 >= 0.0f && o->beta1 < 1.0f) || !(o->beta2 >= 0.0f && o->beta2 < 1.0f))
+            return fail("optimizer: invalid beta parameters (%g, %g)", (double)o->beta1, (double)o->beta2);
+        k->b1 = o->beta1; k->b2 = o->beta2; k->eps = o->eps;
+        if (o->rule == PINN_OPT_ADAMW) k->decay = (float)(1.0 - widen(o->lr) * widen(o->weight_decay));
+    } else if (o->rule == PINN_OPT_SGD) {
+        if (!(o->momentum >= 0.0f)) return fail("optimizer: invalid momentum value %g", (double)o->momentum);
+        if (o->nesterov && (o->momentum <= 0.0f || o->dampening != 0.0f))
+            return fail("optimizer: Nesterov momentum requires a momentum and zero dampening");
+        k->momentum = o->momentum; k->nesterov = o->nesterov ? 1 : 0;
+        k->undamp = (float)(1.0 - widen(o->dampening));
+    } else {
+        if (!(o->eps >= 0.0f)) return fail("optimizer: invalid epsilon value %g", (double)o->eps);
+        if (!(o->momentum >= 0.0f)) return fail("optimizer: invalid momentum value %g", (double)o->momentum);
+        if (!(o->alpha >= 0.0f)) return fail("optimizer: invalid alpha value %g", (double)o->alpha);
+        if (o->momentum > 0.0f && o->centered)
+            return fail("optimizer: RMSprop with momentum AND centered needs three state arrays; the kernels carry two");
+        k->eps = o->eps; k->momentum = o->momentum; k->alpha = o->alpha; k->centered = o->centered ? 1 : 0;
+        k->one_m_alpha = (float)(1.0 - widen(o->alpha));
+    }
+    return 0;
+}
+
+// step_size / bc2_sqrt of a step: Adam's and AdamW's bias corrections (the other rules take none)
+static void optim_scalars(const PinnOptK& k, double step, float* step_size, float* bc2_sqrt) {
+    *step_size = 0.0f; *bc2_sqrt = 1.0f;
+    if (k.rule == PINN_OPT_ADAM || k.rule == PINN_OPT_ADAMW) pinn_adam_scalars(step, k.lr, k.b1, k.b2, step_size, bc2_sqrt);
+}
 
 int launch_reduce(const float* partials, int n_wg, int p_core, float* grads, int accumulate, void* stream,
                   const AdamArgs* adam = nullptr) {
     const int blocks = (p_core + PINN_REDUCE_PB - 1) / PINN_REDUCE_PB;
     const size_t smem = 1024 * sizeof(double);      // (the chunk sums cross the LDS in double: pinn_reduce_kernel)
-    AdamArgs z = {nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0.f, 0.f, 0.f, 0.f, nullptr, -1};
+    AdamArgs z = {nullptr, nullptr, nullptr, nullptr, nullptr, 0, plain_adam(0.f, 0.f, 0.f, 0.f), nullptr, -1};
     const AdamArgs& a = adam ? *adam : z;
     const int do_adam = adam ? 1 : 0;
     float step_size = 0.0f, bc2_sqrt = 1.0f;
-    if (adam) pinn_adam_scalars((double)a.step_value, a.lr, a.b1, a.b2, &step_size, &bc2_sqrt);
+    if (adam) optim_scalars(a.opt, (double)a.step_value, &step_size, &bc2_sqrt);
 #ifdef PINN_EMU
     emu::launch(blocks, 1024, smem, [&] {
         pinn_reduce_kernel(partials, n_wg, p_core, grads, accumulate, do_adam, a.params, a.m, a.v, a.mask, a.step_value,
-                           step_size, bc2_sqrt, a.b1, a.b2, a.eps, a.step_ptr, a.loss_out, a.off_loss, nullptr, 0,
+                           step_size, bc2_sqrt, a.opt, a.step_ptr, a.loss_out, a.off_loss, nullptr, 0,
                            do_adam ? g_fit_next : PinnNextBatch{nullptr, 0, {}, 0u, 0u, 0ull});
     });
 #else
     const PinnFitCtrl* ctrl = do_adam ? g_fit_capture.ctrl : nullptr;
     hipLaunchKernelGGL(pinn_reduce_kernel, dim3(blocks), dim3(1024), smem, (hipStream_t)stream, partials, n_wg, p_core,
-                       grads, accumulate, do_adam, a.params, a.m, a.v, a.mask, a.step_value, step_size, bc2_sqrt, a.b1, a.b2,
-                       a.eps, a.step_ptr, a.loss_out, a.off_loss, ctrl, g_fit_capture.k,
+                       grads, accumulate, do_adam, a.params, a.m, a.v, a.mask, a.step_value, step_size, bc2_sqrt, a.opt,
+                       a.step_ptr, a.loss_out, a.off_loss, ctrl, g_fit_capture.k,
                        do_adam ? g_fit_next : PinnNextBatch{nullptr, 0, {}, 0u, 0u, 0ull});
     if (hipGetLastError() != hipSuccess) return fail("reduce kernel launch failed");
 #endif
@@ -853,7 +915,7 @@ static int run_train(pinn_t* net, PinnKArgs* a, const Plan& plan, int nd, float*
             P.sync = reinterpret_cast<unsigned*>(ws + need + rows_b + state_b);
             if (onecu && a->slab) a->slab = reinterpret_cast<f32x4*>(ws + need + rows_b + state_b + 256);
             P.params = adam->params; P.m = adam->m; P.v = adam->v; P.mask = adam->mask; P.step_ptr = adam->step_ptr; P.grads = grads;
-            P.b1 = adam->b1; P.b2 = adam->b2; P.eps = adam->eps; P.off_loss = net->lay.off_loss;
+            P.opt = adam->opt; P.off_loss = net->lay.off_loss;
 #ifdef PINN_EMU
             memset(P.sync, 0, 256);
 #else
@@ -1035,17 +1097,39 @@ int pinn_residual_step_add(pinn_t* net, const pinn_residual_t* residual, const f
                               grads, workspace, workspace_bytes, stream, nullptr, 1);
 }
 
+// one whole iteration with the update of `opt` in the last reduction launch (the Adam entry points hand in plain_adam(...): Adam's four
+// numbers travel as they always did, unchecked; the family's entry points go through optim_prepare first)
+static int residual_optim_step(pinn_t* net, const pinn_residual_t* residual, float* params, const float* xs,
+                               int64_t n_points, const int* dir_cols, int nd, int n2, const float* ic_streams,
+                               float ic_const, float* grads, float* exp_avg, float* exp_avg_sq, const uint8_t* mask,
+                               int32_t* step_ptr, int32_t step, const PinnOptK& opt,
+                               float* loss_out, void* workspace, size_t workspace_bytes, void* stream) {
+    if (!net || !exp_avg || !exp_avg_sq || !step_ptr) return fail("null argument");
+    if (step < 1) return fail("step must be >= 1");
+    AdamArgs adam = {params, exp_avg, exp_avg_sq, mask, step_ptr, step, opt, loss_out, net->lay.off_loss};
+    // (reduction='sum', pinn_residual_t::crit_sum: no division by the number of points)
+    return residual_step_impl(net, residual, params, xs, n_points, dir_cols, nd, n2, ic_streams, ic_const,
+                              (residual && residual->crit_sum) ? 1.0f : 1.0f / (float)n_points, grads, workspace, workspace_bytes, stream, &adam);
+}
+
 int pinn_residual_adam_step(pinn_t* net, const pinn_residual_t* residual, float* params, const float* xs,
                             int64_t n_points, const int* dir_cols, int nd, int n2, const float* ic_streams,
                             float ic_const, float* grads, float* exp_avg, float* exp_avg_sq, const uint8_t* mask,
                             int32_t* step_ptr, int32_t step, float lr, float beta1, float beta2, float eps,
                             float* loss_out, void* workspace, size_t workspace_bytes, void* stream) {
-    if (!net || !exp_avg || !exp_avg_sq || !step_ptr) return fail("null argument");
-    if (step < 1) return fail("step must be >= 1");
-    AdamArgs adam = {params, exp_avg, exp_avg_sq, mask, step_ptr, step, lr, beta1, beta2, eps, loss_out, net->lay.off_loss};
-    // (reduction='sum', pinn_residual_t::crit_sum: no division by the number of points)
-    return residual_step_impl(net, residual, params, xs, n_points, dir_cols, nd, n2, ic_streams, ic_const,
-                              (residual && residual->crit_sum) ? 1.0f : 1.0f / (float)n_points, grads, workspace, workspace_bytes, stream, &adam);
+    return residual_optim_step(net, residual, params, xs, n_points, dir_cols, nd, n2, ic_streams, ic_const, grads, exp_avg, exp_avg_sq, mask,
+                               step_ptr, step, plain_adam(lr, beta1, beta2, eps), loss_out, workspace, workspace_bytes, stream);
+}
+
+int pinn_residual_optim_step(pinn_t* net, const pinn_residual_t* residual, float* params, const float* xs,
+                             int64_t n_points, const int* dir_cols, int nd, int n2, const float* ic_streams,
+                             float ic_const, float* grads, float* exp_avg, float* exp_avg_sq, const uint8_t* mask,
+                             int32_t* step_ptr, int32_t step, const pinn_optim_t* opt, float* loss_out, void* workspace,
+                             size_t workspace_bytes, void* stream) {
+    PinnOptK k;
+    if (optim_prepare(opt, &k)) return 1;
+    return residual_optim_step(net, residual, params, xs, n_points, dir_cols, nd, n2, ic_streams, ic_const, grads, exp_avg, exp_avg_sq, mask,
+                               step_ptr, step, k, loss_out, workspace, workspace_bytes, stream);
 }
 
 // the sampler description of a fit chunk in the form the reduction's tail takes (non-zero: columns it cannot draw)
@@ -1071,11 +1155,11 @@ static bool single_pass_step(pinn_net* net, const pinn_residual_t* residual, int
     return plan.chunk_tiles >= plan.ntiles;
 }
 
-int pinn_fit_steps(pinn_t* net, const pinn_residual_t* residual, float* params, float* xs, int64_t n_points,
-                   const int* kind, const float* a, const float* b, uint64_t seed, uint64_t call_index0,
-                   const int* dir_cols, int nd, int n2, float ic_const, float* grads, float* exp_avg, float* exp_avg_sq,
-                   const uint8_t* mask, int32_t* step_ptr, int32_t step0, float lr, float beta1, float beta2, float eps,
-                   float* loss_history, int32_t k_steps, void* workspace, size_t workspace_bytes, void* stream) {
+static int fit_steps_impl(pinn_t* net, const pinn_residual_t* residual, float* params, float* xs, int64_t n_points,
+                          const int* kind, const float* a, const float* b, uint64_t seed, uint64_t call_index0,
+                          const int* dir_cols, int nd, int n2, float ic_const, float* grads, float* exp_avg, float* exp_avg_sq,
+                          const uint8_t* mask, int32_t* step_ptr, int32_t step0, const PinnOptK& opt,
+                          float* loss_history, int32_t k_steps, void* workspace, size_t workspace_bytes, void* stream) {
     if (!net || !xs || !loss_history) return fail("null argument");
     if (k_steps < 0 || step0 < 1) return fail("k_steps must be >= 0 and step0 >= 1");
     // K iterations of the reference's fit loop (model_torch.py:426-464) enqueued by ONE call: sample, fused step, Adam. Nothing
@@ -1091,12 +1175,33 @@ int pinn_fit_steps(pinn_t* net, const pinn_residual_t* residual, float* params, 
         if (k == 0 || !hand_over) rc = pinn_sample_points(xs, n_points, net->lay.d, kind, a, b, seed, call_index0 + (uint64_t)k, stream);
         if (rc) break;
         if (hand_over && k + 1 < k_steps) { next.call = call_index0 + (uint64_t)k + 1; g_fit_next = next; }
-        rc = pinn_residual_adam_step(net, residual, params, xs, n_points, dir_cols, nd, n2, nullptr, ic_const, grads, exp_avg,
-                                     exp_avg_sq, mask, step_ptr, step0 + k, lr, beta1, beta2, eps, loss_history + k, workspace,
-                                     workspace_bytes, stream);
+        rc = residual_optim_step(net, residual, params, xs, n_points, dir_cols, nd, n2, nullptr, ic_const, grads, exp_avg,
+                                 exp_avg_sq, mask, step_ptr, step0 + k, opt, loss_history + k, workspace,
+                                 workspace_bytes, stream);
         g_fit_next.n = 0;
     }
     return rc;
+}
+
+int pinn_fit_steps(pinn_t* net, const pinn_residual_t* residual, float* params, float* xs, int64_t n_points,
+                   const int* kind, const float* a, const float* b, uint64_t seed, uint64_t call_index0,
+                   const int* dir_cols, int nd, int n2, float ic_const, float* grads, float* exp_avg, float* exp_avg_sq,
+                   const uint8_t* mask, int32_t* step_ptr, int32_t step0, float lr, float beta1, float beta2, float eps,
+                   float* loss_history, int32_t k_steps, void* workspace, size_t workspace_bytes, void* stream) {
+    return fit_steps_impl(net, residual, params, xs, n_points, kind, a, b, seed, call_index0, dir_cols, nd, n2, ic_const, grads, exp_avg,
+                          exp_avg_sq, mask, step_ptr, step0, plain_adam(lr, beta1, beta2, eps), loss_history, k_steps, workspace,
+                          workspace_bytes, stream);
+}
+
+int pinn_fit_steps_optim(pinn_t* net, const pinn_residual_t* residual, float* params, float* xs, int64_t n_points,
+                         const int* kind, const float* a, const float* b, uint64_t seed, uint64_t call_index0,
+                         const int* dir_cols, int nd, int n2, float ic_const, float* grads, float* exp_avg, float* exp_avg_sq,
+                         const uint8_t* mask, int32_t* step_ptr, int32_t step0, const pinn_optim_t* opt,
+                         float* loss_history, int32_t k_steps, void* workspace, size_t workspace_bytes, void* stream) {
+    PinnOptK k;
+    if (optim_prepare(opt, &k)) return 1;
+    return fit_steps_impl(net, residual, params, xs, n_points, kind, a, b, seed, call_index0, dir_cols, nd, n2, ic_const, grads, exp_avg,
+                          exp_avg_sq, mask, step_ptr, step0, k, loss_history, k_steps, workspace, workspace_bytes, stream);
 }
 
 size_t pinn_fit_ctrl_bytes(void) { return sizeof(PinnFitCtrl); }
@@ -1117,12 +1222,12 @@ static void key_mix(unsigned long long (&key)[4], const void* p, size_t n) {
     }
 }
 
-int pinn_fit_steps_graph(pinn_t* net, const pinn_residual_t* residual, float* params, float* xs, int64_t n_points,
-                         const int* kind, const float* a, const float* b, uint64_t seed, uint64_t call_index0,
-                         const int* dir_cols, int nd, int n2, float ic_const, float* grads, float* exp_avg, float* exp_avg_sq,
-                         const uint8_t* mask, int32_t* step_ptr, int32_t step0, float lr, float beta1, float beta2, float eps,
-                         float* loss_history, int32_t k_steps, void* workspace, size_t workspace_bytes, void* ctrl,
-                         size_t ctrl_bytes, void* stream) {
+static int fit_steps_graph_impl(pinn_t* net, const pinn_residual_t* residual, float* params, float* xs, int64_t n_points,
+                                const int* kind, const float* a, const float* b, uint64_t seed, uint64_t call_index0,
+                                const int* dir_cols, int nd, int n2, float ic_const, float* grads, float* exp_avg, float* exp_avg_sq,
+                                const uint8_t* mask, int32_t* step_ptr, int32_t step0, const PinnOptK& opt,
+                                float* loss_history, int32_t k_steps, void* workspace, size_t workspace_bytes, void* ctrl,
+                                size_t ctrl_bytes, void* stream) {
     if (!net || !residual || !xs || !loss_history || !kind || !a || !b || !dir_cols) return fail("null argument");
     if (k_steps < 0 || step0 < 1) return fail("k_steps must be >= 0 and step0 >= 1");
     // narrow nets, batches of a few tiles: the whole chunk -- any length up to PINN_FIT_CHUNK_MAX -- as ONE launch (pinn_fit_kernel.h);
@@ -1137,7 +1242,7 @@ int pinn_fit_steps_graph(pinn_t* net, const pinn_residual_t* residual, float* pa
             ca.c.k0 = (unsigned)(seed & 0xffffffffull); ca.c.k1 = (unsigned)(seed >> 32);
             for (int k = 0; k < PINN_FIT_CHUNK_MAX; ++k) {
                 ca.c.step_size[k] = 0.0f; ca.c.bc2_sqrt[k] = 1.0f;
-                if (k < k_steps) pinn_adam_scalars((double)(step0 + k), lr, beta1, beta2, &ca.c.step_size[k], &ca.c.bc2_sqrt[k]);
+                if (k < k_steps) optim_scalars(opt, (double)(step0 + k), &ca.c.step_size[k], &ca.c.bc2_sqrt[k]);
             }
             memset(&g_fit_persist, 0, sizeof(g_fit_persist));
             PinnFitP& P = g_fit_persist.p;
@@ -1151,8 +1256,8 @@ int pinn_fit_steps_graph(pinn_t* net, const pinn_residual_t* residual, float* pa
             const int rc0 = (hipGetLastError() != hipSuccess) ? fail("control-block launch failed") : 0;
 #endif
             const int rc = rc0 ? rc0
-                           : pinn_residual_adam_step(net, residual, params, xs, n_points, dir_cols, nd, n2, nullptr, ic_const, grads, exp_avg,
-                                                     exp_avg_sq, mask, step_ptr, step0, lr, beta1, beta2, eps, loss_history, workspace,
+                           : residual_optim_step(net, residual, params, xs, n_points, dir_cols, nd, n2, nullptr, ic_const, grads, exp_avg,
+                                                     exp_avg_sq, mask, step_ptr, step0, opt, loss_history, workspace,
                                                      workspace_bytes, stream);
             const int did = g_fit_persist.done;
             g_fit_persist.active = 0;
@@ -1161,14 +1266,14 @@ int pinn_fit_steps_graph(pinn_t* net, const pinn_residual_t* residual, float* pa
         }
     }
 #ifdef PINN_EMU
-    return pinn_fit_steps(net, residual, params, xs, n_points, kind, a, b, seed, call_index0, dir_cols, nd, n2, ic_const, grads, exp_avg,
-                          exp_avg_sq, mask, step_ptr, step0, lr, beta1, beta2, eps, loss_history, k_steps, workspace, workspace_bytes, stream);
+    return fit_steps_impl(net, residual, params, xs, n_points, kind, a, b, seed, call_index0, dir_cols, nd, n2, ic_const, grads, exp_avg,
+                          exp_avg_sq, mask, step_ptr, step0, opt, loss_history, k_steps, workspace, workspace_bytes, stream);
 #else
     // the graph pays where launch gaps are a visible share of an iteration; chunks that do not qualify run the eager loop
     // (only whole chunks: the tail of a fit would capture a graph of its own that nothing replays)
     if (k_steps != PINN_FIT_CHUNK_MAX || !ctrl || ctrl_bytes < sizeof(PinnFitCtrl) || g_profile || g_phase_prof)
-        return pinn_fit_steps(net, residual, params, xs, n_points, kind, a, b, seed, call_index0, dir_cols, nd, n2, ic_const, grads, exp_avg,
-                              exp_avg_sq, mask, step_ptr, step0, lr, beta1, beta2, eps, loss_history, k_steps, workspace, workspace_bytes, stream);
+        return fit_steps_impl(net, residual, params, xs, n_points, kind, a, b, seed, call_index0, dir_cols, nd, n2, ic_const, grads, exp_avg,
+                              exp_avg_sq, mask, step_ptr, step0, opt, loss_history, k_steps, workspace, workspace_bytes, stream);
     // everything the captured launches carry BY VALUE or by address (the per-iteration values travel through the control block)
     unsigned long long key[4] = {14695981039346656037ull, 14695981039346656037ull ^ 1, 14695981039346656037ull ^ 2, 14695981039346656037ull ^ 3};
     key_mix(key, residual, sizeof(*residual));
@@ -1178,7 +1283,9 @@ int pinn_fit_steps_graph(pinn_t* net, const pinn_residual_t* residual, float* pa
     const long long ints[] = {(long long)n_points, nd, n2, (long long)workspace_bytes, net->gemm_mode, net->tanh_mode, net->max_per_cu,
                               net->prepass_in_kernel, (long long)net->wgx_chunk_bytes};
     key_mix(key, ints, sizeof(ints));
-    const float flts[] = {ic_const, lr, beta1, beta2, eps, residual->crit_param};
+    const float flts[] = {ic_const, residual->crit_param};
+    // (the update rule with its hyper-parameters: the reductions of the recorded chunk carry it by value)
+    key_mix(key, &opt, sizeof(opt));
     // (the criterion is part of `residual`, hashed above; named here once more so that the key does not depend on where the fields sit)
     const int crit_key[] = {residual->criterion, residual->crit_sum};
     key_mix(key, crit_key, sizeof(crit_key));
@@ -1195,8 +1302,8 @@ int pinn_fit_steps_graph(pinn_t* net, const pinn_residual_t* residual, float* pa
         if (net->fit_graph_exec) { (void)hipGraphExecDestroy((hipGraphExec_t)net->fit_graph_exec); net->fit_graph_exec = nullptr; }
         // one eager iteration's worth of planning has to have happened (function attributes, occupancy queries are not capturable):
         // the first chunk of a configuration runs eagerly AND is followed by the capture of the graph the next chunks replay
-        const int rc = pinn_fit_steps(net, residual, params, xs, n_points, kind, a, b, seed, call_index0, dir_cols, nd, n2, ic_const, grads,
-                                      exp_avg, exp_avg_sq, mask, step_ptr, step0, lr, beta1, beta2, eps, loss_history, k_steps, workspace,
+        const int rc = fit_steps_impl(net, residual, params, xs, n_points, kind, a, b, seed, call_index0, dir_cols, nd, n2, ic_const, grads,
+                                      exp_avg, exp_avg_sq, mask, step_ptr, step0, opt, loss_history, k_steps, workspace,
                                       workspace_bytes, stream);
         if (rc) return rc;
         hipGraph_t graph = nullptr;
@@ -1215,8 +1322,8 @@ int pinn_fit_steps_graph(pinn_t* net, const pinn_residual_t* residual, float* pa
             // (the by-value step numbers and loss slots of the captured launches are placeholders: the kernels read the control block)
             if (k == 0 || !cap_hand_over) crc = pinn_sample_points(xs, n_points, net->lay.d, kind, a, b, seed, 0, cs);
             if (cap_hand_over && k + 1 < k_steps) g_fit_next = cap_next;
-            if (!crc) crc = pinn_residual_adam_step(net, residual, params, xs, n_points, dir_cols, nd, n2, nullptr, ic_const, grads, exp_avg,
-                                                    exp_avg_sq, mask, step_ptr, 1, lr, beta1, beta2, eps, loss_history, workspace,
+            if (!crc) crc = residual_optim_step(net, residual, params, xs, n_points, dir_cols, nd, n2, nullptr, ic_const, grads, exp_avg,
+                                                    exp_avg_sq, mask, step_ptr, 1, opt, loss_history, workspace,
                                                     workspace_bytes, cs);
             g_fit_next.n = 0;       // (as in the eager loop: the LAST reduction of a chunk draws nothing -- ADVICE r4)
         }
@@ -1243,7 +1350,7 @@ int pinn_fit_steps_graph(pinn_t* net, const pinn_residual_t* residual, float* pa
     ca.c.k0 = (unsigned)(seed & 0xffffffffull); ca.c.k1 = (unsigned)(seed >> 32);
     for (int k = 0; k < PINN_FIT_CHUNK_MAX; ++k) {
         ca.c.step_size[k] = 0.0f; ca.c.bc2_sqrt[k] = 1.0f;
-        if (k < k_steps) pinn_adam_scalars((double)(step0 + k), lr, beta1, beta2, &ca.c.step_size[k], &ca.c.bc2_sqrt[k]);
+        if (k < k_steps) optim_scalars(opt, (double)(step0 + k), &ca.c.step_size[k], &ca.c.bc2_sqrt[k]);
     }
     hipLaunchKernelGGL(pinn_fit_ctrl_kernel, dim3(1), dim3(128), 0, hs, dctrl, ca);
     if (hipGetLastError() != hipSuccess) return fail("control-block launch failed");
@@ -1253,30 +1360,53 @@ int pinn_fit_steps_graph(pinn_t* net, const pinn_residual_t* residual, float* pa
 #endif
 }
 
-static int adam_launch(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, const uint8_t* mask, int64_t n,
-                       int32_t* step_ptr, int32_t step, float lr, float beta1, float beta2, float eps, void* stream,
-                       float* loss_out = nullptr, int off_loss = -1) {
+int pinn_fit_steps_graph(pinn_t* net, const pinn_residual_t* residual, float* params, float* xs, int64_t n_points,
+                         const int* kind, const float* a, const float* b, uint64_t seed, uint64_t call_index0,
+                         const int* dir_cols, int nd, int n2, float ic_const, float* grads, float* exp_avg, float* exp_avg_sq,
+                         const uint8_t* mask, int32_t* step_ptr, int32_t step0, float lr, float beta1, float beta2, float eps,
+                         float* loss_history, int32_t k_steps, void* workspace, size_t workspace_bytes, void* ctrl,
+                         size_t ctrl_bytes, void* stream) {
+    return fit_steps_graph_impl(net, residual, params, xs, n_points, kind, a, b, seed, call_index0, dir_cols, nd, n2, ic_const, grads, exp_avg,
+                                exp_avg_sq, mask, step_ptr, step0, plain_adam(lr, beta1, beta2, eps), loss_history, k_steps, workspace,
+                                workspace_bytes, ctrl, ctrl_bytes, stream);
+}
+
+int pinn_fit_steps_optim_graph(pinn_t* net, const pinn_residual_t* residual, float* params, float* xs, int64_t n_points,
+                               const int* kind, const float* a, const float* b, uint64_t seed, uint64_t call_index0,
+                               const int* dir_cols, int nd, int n2, float ic_const, float* grads, float* exp_avg, float* exp_avg_sq,
+                               const uint8_t* mask, int32_t* step_ptr, int32_t step0, const pinn_optim_t* opt,
+                               float* loss_history, int32_t k_steps, void* workspace, size_t workspace_bytes, void* ctrl,
+                               size_t ctrl_bytes, void* stream) {
+    PinnOptK k;
+    if (optim_prepare(opt, &k)) return 1;
+    return fit_steps_graph_impl(net, residual, params, xs, n_points, kind, a, b, seed, call_index0, dir_cols, nd, n2, ic_const, grads, exp_avg,
+                                exp_avg_sq, mask, step_ptr, step0, k, loss_history, k_steps, workspace, workspace_bytes, ctrl, ctrl_bytes,
+                                stream);
+}
+
+static int optim_launch(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, const uint8_t* mask, int64_t n,
+                        int32_t* step_ptr, int32_t step, const PinnOptK& opt, void* stream,
+                        float* loss_out = nullptr, int off_loss = -1) {
     if (!params || !grads || !exp_avg || !exp_avg_sq || !step_ptr) return fail("null argument");
     if (n <= 0) return 0;
     const int blocks = (int)((n + 255) / 256);
     float step_size = 0.0f, bc2_sqrt = 1.0f;
-    if (step > 0) pinn_adam_scalars((double)step, lr, beta1, beta2, &step_size, &bc2_sqrt);
+    if (step > 0) optim_scalars(opt, (double)step, &step_size, &bc2_sqrt);
 #ifdef PINN_EMU
     if (step <= 0) emu::launch(1, 64, 0, [&] { pinn_tick_kernel(step_ptr); });
-    emu::launch(blocks, 256, 0, [&] { pinn_adam_kernel(params, grads, exp_avg, exp_avg_sq, mask, n, step_ptr, step, lr, step_size, bc2_sqrt, beta1, beta2, eps, loss_out, off_loss); });
+    emu::launch(blocks, 256, 0, [&] { pinn_optim_kernel(params, grads, exp_avg, exp_avg_sq, mask, n, step_ptr, step, step_size, bc2_sqrt, opt, loss_out, off_loss); });
 #else
     if (step <= 0) hipLaunchKernelGGL(pinn_tick_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, step_ptr);
-    hipLaunchKernelGGL(pinn_adam_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, params, grads, exp_avg,
-                       exp_avg_sq, mask, (long long)n, (int*)step_ptr, (int)step, lr, step_size, bc2_sqrt, beta1, beta2, eps,
-                       loss_out, off_loss);
-    if (hipGetLastError() != hipSuccess) return fail("adam kernel launch failed");
+    hipLaunchKernelGGL(pinn_optim_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, params, grads, exp_avg,
+                       exp_avg_sq, mask, (long long)n, (int*)step_ptr, (int)step, step_size, bc2_sqrt, opt, loss_out, off_loss);
+    if (hipGetLastError() != hipSuccess) return fail("optimizer kernel launch failed");
 #endif
     return 0;
 }
 
 int pinn_adam_step(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, const uint8_t* mask, int64_t n,
                    int32_t* step_ptr, float lr, float beta1, float beta2, float eps, void* stream) {
-    return adam_launch(params, grads, exp_avg, exp_avg_sq, mask, n, step_ptr, 0, lr, beta1, beta2, eps, stream);
+    return optim_launch(params, grads, exp_avg, exp_avg_sq, mask, n, step_ptr, 0, plain_adam(lr, beta1, beta2, eps), stream);
 }
 
 int pinn_adam_step_at(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, const uint8_t* mask, int64_t n,
@@ -1284,8 +1414,24 @@ int pinn_adam_step_at(float* params, const float* grads, float* exp_avg, float* 
                       int32_t off_loss, void* stream) {
     if (step < 1) return fail("step must be >= 1");
     if (loss_out && (off_loss < 0 || off_loss >= n)) return fail("off_loss=%d outside the gradient buffer", off_loss);
-    return adam_launch(params, grads, exp_avg, exp_avg_sq, mask, n, step_ptr, step, lr, beta1, beta2, eps, stream, loss_out,
-                       off_loss);
+    return optim_launch(params, grads, exp_avg, exp_avg_sq, mask, n, step_ptr, step, plain_adam(lr, beta1, beta2, eps), stream, loss_out,
+                        off_loss);
+}
+
+int pinn_optim_step(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, const uint8_t* mask, int64_t n,
+                    int32_t* step_ptr, const pinn_optim_t* opt, void* stream) {
+    PinnOptK k;
+    if (optim_prepare(opt, &k)) return 1;
+    return optim_launch(params, grads, exp_avg, exp_avg_sq, mask, n, step_ptr, 0, k, stream);
+}
+
+int pinn_optim_step_at(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, const uint8_t* mask, int64_t n,
+                       int32_t* step_ptr, int32_t step, const pinn_optim_t* opt, float* loss_out, int32_t off_loss, void* stream) {
+    PinnOptK k;
+    if (optim_prepare(opt, &k)) return 1;
+    if (step < 1) return fail("step must be >= 1");
+    if (loss_out && (off_loss < 0 || off_loss >= n)) return fail("off_loss=%d outside the gradient buffer", off_loss);
+    return optim_launch(params, grads, exp_avg, exp_avg_sq, mask, n, step_ptr, step, k, stream, loss_out, off_loss);
 }
 
 }  // extern "C"

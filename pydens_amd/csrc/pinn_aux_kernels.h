@@ -48,9 +48,65 @@ PINN_DEVICE void pinn_adam_apply(float* params, float* m, float* v, long long i,
     params[i] = p_old - step_size * (mi / denom);
 }
 
-PINN_DEVICE void pinn_adam_update(float* params, float gi, float* m, float* v, long long i, float step_size, float bc2_sqrt,
-                                  float b1, float b2, float eps) {
-    pinn_adam_apply(params, m, v, i, gi, m[i], v[i], params[i], step_size, bc2_sqrt, b1, b2, eps);
+// ------------------------------------------------------------------------------------------------------------
+// The optimizer family (include/pinn.h pinn_optim_t): the `_single_tensor_*` arithmetic of torch.optim.{Adam, AdamW, SGD, RMSprop},
+// one expression tree per rule, shared by every caller (pinn_reduce_kernel's tail, pinn_optim_kernel, sweep (d) of pinn_fit_kernel).
+// The rule is a wave-uniform code in the kernel arguments, like the criterion of the point stage. What torch computes once per
+// step as a Python double (1 - lr * weight_decay, 1 - dampening, 1 - alpha) is derived on the host (pinn_abi.cpp optim_prepare).
+// ------------------------------------------------------------------------------------------------------------
+struct PinnOptK {
+    int rule, nesterov, centered, pad;
+    float lr, b1, b2, eps, wd, momentum, alpha;
+    float decay;            // AdamW: 1 - lr * weight_decay
+    float undamp;           // SGD: 1 - dampening
+    float one_m_alpha;      // RMSprop: 1 - alpha
+};
+
+// m / v: the two state arrays (exp_avg | momentum_buffer | grad_avg, exp_avg_sq | square_avg); `first`: step 1 of the optimizer (SGD: no
+// momentum buffer yet). A rule writes only the state it owns.
+PINN_DEVICE void pinn_optim_apply(const PinnOptK& o, float* params, float* m, float* v, long long i, float gi, float m_old, float v_old,
+                                  float p_old, float step_size, float bc2_sqrt, bool first) {
+    if (o.rule == PINN_OPT_ADAM && o.wd == 0.0f) {          // (plain Adam: the arithmetic the library had before the family existed)
+        pinn_adam_apply(params, m, v, i, gi, m_old, v_old, p_old, step_size, bc2_sqrt, o.b1, o.b2, o.eps);
+        return;
+    }
+    if (o.rule == PINN_OPT_ADAMW) p_old *= o.decay;                         // param.mul_(1 - lr * weight_decay)
+    else if (o.wd != 0.0f) gi = fmaf(o.wd, p_old, gi);                      // grad = grad.add(param, alpha=weight_decay)
+    if (o.rule == PINN_OPT_ADAM || o.rule == PINN_OPT_ADAMW) {
+        pinn_adam_apply(params, m, v, i, gi, m_old, v_old, p_old, step_size, bc2_sqrt, o.b1, o.b2, o.eps);
+    } else if (o.rule == PINN_OPT_SGD) {
+        if (o.momentum != 0.0f) {
+            // buf = clone(grad) on the first step, else buf.mul_(momentum).add_(grad, alpha=1 - dampening)
+            const float buf = first ? gi : fmaf(o.undamp, gi, o.momentum * m_old);
+            m[i] = buf;
+            gi = o.nesterov ? fmaf(o.momentum, buf, gi) : buf;              // grad.add(buf, alpha=momentum)
+        }
+        params[i] = p_old - o.lr * gi;                                      // param.add_(grad, alpha=-lr)
+    } else {                                                                // PINN_OPT_RMSPROP
+        const float sq = fmaf(o.one_m_alpha, gi * gi, o.alpha * v_old);     // square_avg.mul_(alpha).addcmul_(grad, grad, value=1 - alpha)
+        v[i] = sq;
+        float avg;
+        if (o.centered) {
+            const float ga = m_old + o.one_m_alpha * (gi - m_old);          // grad_avg.lerp_(grad, 1 - alpha)
+            m[i] = ga;
+            avg = sqrtf(fmaf(-ga, ga, sq));                                 // square_avg.addcmul(grad_avg, grad_avg, value=-1).sqrt_()
+        } else {
+            avg = sqrtf(sq);
+        }
+        avg += o.eps;
+        if (o.momentum > 0.0f) {
+            const float buf = fmaf(o.momentum, m_old, gi / avg);            // buf.mul_(momentum).addcdiv_(grad, avg)
+            m[i] = buf;
+            params[i] = p_old - o.lr * buf;
+        } else {
+            params[i] = p_old - o.lr * (gi / avg);                          // param.addcdiv_(grad, avg, value=-lr)
+        }
+    }
+}
+
+PINN_DEVICE void pinn_optim_update(const PinnOptK& o, float* params, float gi, float* m, float* v, long long i, float step_size,
+                                   float bc2_sqrt, bool first) {
+    pinn_optim_apply(o, params, m, v, i, gi, m[i], v[i], params[i], step_size, bc2_sqrt, first);
 }
 
 #ifndef PINN_REDUCE_PB
@@ -145,9 +201,8 @@ PINN_AUX_GLOBAL void PINN_LAUNCH_BOUNDS(128) pinn_fit_ctrl_kernel(PinnFitCtrl* d
 
 PINN_AUX_GLOBAL void PINN_LAUNCH_BOUNDS(1024)
 pinn_reduce_kernel(const float* partials, int n_wg, int p_core, float* grads, int accumulate, int do_adam, float* params,
-                   float* m, float* v, const unsigned char* mask, int step_value, float step_size, float bc2_sqrt, float b1,
-                   float b2, float eps, int* step_ptr, float* loss_out, int off_loss, const PinnFitCtrl* ctrl, int ctrl_k,
-                   PinnNextBatch next) {
+                   float* m, float* v, const unsigned char* mask, int step_value, float step_size, float bc2_sqrt, PinnOptK opt,
+                   int* step_ptr, float* loss_out, int off_loss, const PinnFitCtrl* ctrl, int ctrl_k, PinnNextBatch next) {
     PINN_SMEM(red);
     const int tid = PINN_TID;
     if (ctrl) {             // (graph replay: this iteration's Adam step and loss slot come from the control block)
@@ -201,7 +256,7 @@ pinn_reduce_kernel(const float* partials, int n_wg, int p_core, float* grads, in
         const float t = (float)t64;
         grads[p] = t;
         if (loss_out && p == off_loss) loss_out[0] = t;
-        if (upd) pinn_adam_apply(params, m, v, p, t, m_old, v_old, p_old, step_size, bc2_sqrt, b1, b2, eps);
+        if (upd) pinn_optim_apply(opt, params, m, v, p, t, m_old, v_old, p_old, step_size, bc2_sqrt, step_value == 1);
     }
     if (do_adam && PINN_BID == 0 && tid == 0) step_ptr[0] = step_value;
     // fit chunks: this iteration's tile kernel is through with the batch buffer -- the batch of the next iteration is drawn here
@@ -216,7 +271,7 @@ pinn_reduce_kernel(const float* partials, int n_wg, int p_core, float* grads, in
 }
 
 // ------------------------------------------------------------------------------------------------------------
-// Adam (torch.optim.Adam single-tensor form, model_torch.py:461): exp_avg/exp_avg_sq EMA, bias-corrected step
+// Standalone update (torch.optim single-tensor forms, model_torch.py:461): pinn_optim_kernel below
 // ------------------------------------------------------------------------------------------------------------
 // wt[l][in][out] = W_l[out][in] for the lh hidden->hidden matrices (hp x hp, row stride hp, layer stride hidden_stride):
 // 32 x 32 tiles through LDS, both sides coalesced. Grid: (hp/32)^2 * lh workgroups of 256 threads.
@@ -267,9 +322,8 @@ PINN_AUX_GLOBAL void PINN_LAUNCH_BOUNDS(64) pinn_tick_kernel(int* step_ptr) {
 }
 
 PINN_AUX_GLOBAL void PINN_LAUNCH_BOUNDS(256)
-pinn_adam_kernel(float* params, const float* grads, float* m, float* v, const unsigned char* mask, long long n,
-                 int* step_ptr, int step_value, float lr, float step_size, float bc2_sqrt, float b1, float b2, float eps,
-                 float* loss_out, int off_loss) {
+pinn_optim_kernel(float* params, const float* grads, float* m, float* v, const unsigned char* mask, long long n,
+                  int* step_ptr, int step_value, float step_size, float bc2_sqrt, PinnOptK opt, float* loss_out, int off_loss) {
     // step_value > 0: the host counts (step_size / bc2_sqrt come with it, the count is mirrored to step_ptr); otherwise
     // the count lives on the device and the bias corrections are computed here
     // loss_out: the loss slot of the (all-reduced) gradient buffer is copied to one more address -- entry i of the host's
@@ -279,8 +333,12 @@ pinn_adam_kernel(float* params, const float* grads, float* m, float* v, const un
     if (loss_out && i == 0) loss_out[0] = grads[off_loss];
     if (i >= n) return;
     if (mask && !mask[i]) return;
-    if (step_value <= 0) pinn_adam_scalars((double)step_ptr[0], lr, b1, b2, &step_size, &bc2_sqrt);
-    pinn_adam_update(params, grads[i], m, v, i, step_size, bc2_sqrt, b1, b2, eps);
+    // (the bias corrections are Adam's and AdamW's; SGD needs "is this step 1", RMSprop nothing)
+    if (step_value <= 0) {
+        step_value = step_ptr[0];
+        if (opt.rule == PINN_OPT_ADAM || opt.rule == PINN_OPT_ADAMW) pinn_adam_scalars((double)step_value, opt.lr, opt.b1, opt.b2, &step_size, &bc2_sqrt);
+    }
+    pinn_optim_update(opt, params, grads[i], m, v, i, step_size, bc2_sqrt, step_value == 1);
 }
 
 // one thread per point. Counter = (point low, point high, call low, call high | block << 28): block b < 8 supplies the

@@ -39,7 +39,7 @@ struct PinnFitP {
     float* state;                       // [grid][3][p_core] (parameters | exp_avg | exp_avg_sq) of every workgroup
     unsigned* sync;                     // [0] arrival counter, [1] error flag; zeroed by the host in front of the launch
     float* xs; long long n; PinnSampleSpec spec;
-    float b1, b2, eps;
+    PinnOptK opt;                       // the update rule (pinn_aux_kernels.h)
     int off_loss;
 };
 
@@ -114,6 +114,13 @@ pinn_fit_kernel(const PinnKArgs A0, const PinnFitP P) {
 #ifndef PINN_EMU
     __shared__ unsigned bail;        // (grid form only)
     if (!RES && gtid == 0) bail = 0u;
+    // the update rule waits in LDS for sweep (d): as kernel arguments its fourteen words stayed in scalar registers across the tile pass
+    // (compiled for 256 registers at two waves per SIMD) and came out as spills
+    __shared__ PinnOptK opt_lds;
+    if (gtid == 0) opt_lds = P.opt;
+    const PinnOptK& opt = opt_lds;
+#else
+    const PinnOptK& opt = P.opt;
 #endif
     PINN_FENCE_BLOCK();
     PINN_SYNC();
@@ -133,8 +140,10 @@ pinn_fit_kernel(const PinnKArgs A0, const PinnFitP P) {
 #pragma unroll
     for (int q = 0; q < 4; ++q) { const int p = gtid + q * NTH; upd[q] = (p < pc) && (!P.mask || P.mask[p]); }
     const unsigned long long call0 = ctrl->call_index0;
+    const int step0 = ctrl->step0;
     for (int k = 0; k < P.k_steps; ++k) {
         const float step_size = ctrl->step_size[k], bc2_sqrt = ctrl->bc2_sqrt[k];     // (fetched here: the loads ride behind the tile pass)
+        const bool first = step0 + k == 1;                                            // (SGD: no momentum buffer yet)
         // (a) the batch of iteration k, the points of this (virtual) workgroup's tiles only (the tile body reads nothing else). The
         //     one-CU form draws the batch of iteration k + 1 at the end of (d) instead -- the tile pass is through with the buffer by
         //     then, and the barrier that closes (d) covers it: one barrier and one wait for the stores less per iteration
@@ -202,7 +211,7 @@ pinn_fit_kernel(const PinnKArgs A0, const PinnFitP P) {
                     if (k + 1 == P.k_steps) P.grads[p] = t[q];
                     if (p == P.off_loss) ctrl->loss_base[k] = t[q];
                 }
-                if (mask_reg ? upd[q] : (!P.mask || P.mask[p])) pinn_adam_update(my, t[q], my + sst, my + 2 * sst, p, step_size, bc2_sqrt, P.b1, P.b2, P.eps);
+                if (mask_reg ? upd[q] : (!P.mask || P.mask[p])) pinn_optim_update(opt, my, t[q], my + sst, my + 2 * sst, p, step_size, bc2_sqrt, first);
             }
         }
         if (RES && k + 1 < P.k_steps) draw(k + 1);

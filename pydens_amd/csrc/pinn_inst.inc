@@ -160,7 +160,7 @@ int launch_one(const PinnKArgs* a, int grid, void* stream, int query, long long*
                 if constexpr (FIT_VW >= 2) {
                     // LDS: the virtual workgroups' blocks + W^T, then what stays resident (state, rows, batch, pre-pass rows)
                     const long long res_bytes = 4 * (FV::BASE_FLOATS + FV::resident_floats(a->p_core, fp->n, a->d, a->n_aux));
-                    if (res_bytes > 160 * 1024 - 64) return 1;
+                    if (res_bytes > 160 * 1024 - 128) return 1;       // (the rest: pinn_fit_kernel's static LDS -- bail flag, update rule)
 #ifdef PINN_EMU
                     const PinnKArgs args = *a; const PinnFitP fargs = *fp;
                     emu::launch(1, C::NTHREADS * FIT_VW, (size_t)res_bytes,
@@ -168,7 +168,7 @@ int launch_one(const PinnKArgs* a, int grid, void* stream, int query, long long*
 #else
                     static unsigned long long fit1_attr_done = 0;
                     if (pinn_set_smem_attr(reinterpret_cast<const void*>(&pinn_fit_kernel<PINN_INST_HP, ND, N2, MT, LHC, ACTC, COMB, VAR, FIT_VW>),
-                                           160 * 1024 - 64, fit1_attr_done)) return 2;
+                                           160 * 1024 - 128, fit1_attr_done)) return 2;
                     hipLaunchKernelGGL((pinn_fit_kernel<PINN_INST_HP, ND, N2, MT, LHC, ACTC, COMB, VAR, FIT_VW>), dim3(1),
                                        dim3(C::NTHREADS * FIT_VW), (size_t)res_bytes, (hipStream_t)stream, *a, *fp);
 #endif

@@ -19,6 +19,7 @@ MAX_STREAMS, MAX_AUX, MAX_VARS = 7, 8, 8
 SAMPLE_UNIFORM, SAMPLE_NORMAL, SAMPLE_CONST = 0, 1, 2
 RES_PROGRAM, RES_AFFINE = 0, 1
 CRIT_MSE, CRIT_L1, CRIT_SMOOTH_L1, CRIT_HUBER = 0, 1, 2, 3      # include/pinn.h PINN_CRIT_*
+OPT_ADAM, OPT_ADAMW, OPT_SGD, OPT_RMSPROP = 0, 1, 2, 3             # include/pinn.h PINN_OPT_*
 SKIP_PRE = 0x100         # include/pinn.h PINN_SKIP_PRE
 ACT_CODES = {'tanh': 0, 'sigmoid': 1, 'sin': 2, 'identity': 3, 'softplus': 4, 'silu': 5, 'swish': 5, 'gelu': 6,
              # round 5 (include/pinn.h PINN_ACT_RELU ..): torch-default forms
@@ -92,6 +93,22 @@ class Residual(ctypes.Structure):
         return res
 
 
+class Optim(ctypes.Structure):
+    """ pinn_optim_t: the update rule of the optimizer entry points with torch.optim's hyper-parameters (all zero but Adam's four: plain Adam) """
+    _fields_ = [('rule', ctypes.c_int)] + [(name, ctypes.c_float) for name in
+                                           ('lr', 'beta1', 'beta2', 'eps', 'weight_decay', 'momentum', 'dampening', 'alpha')] + \
+               [('nesterov', ctypes.c_int), ('centered', ctypes.c_int)]
+
+    @classmethod
+    def build(cls, rule, lr, betas=(0.0, 0.0), eps=0.0, weight_decay=0.0, momentum=0.0, dampening=0.0, alpha=0.0, nesterov=False,
+              centered=False):
+        opt = cls()
+        opt.rule, opt.lr, opt.beta1, opt.beta2, opt.eps = int(rule), float(lr), float(betas[0]), float(betas[1]), float(eps)
+        opt.weight_decay, opt.momentum, opt.dampening, opt.alpha = float(weight_decay), float(momentum), float(dampening), float(alpha)
+        opt.nesterov, opt.centered = int(bool(nesterov)), int(bool(centered))
+        return opt
+
+
 def bind(lib):
     """ declare the signatures of include/pinn.h on a loaded shared library. """
     vp, i32, i64, f32 = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_float
@@ -128,6 +145,18 @@ def bind(lib):
                                          vp, i32, vp, ctypes.c_size_t, vp, ctypes.c_size_t, vp]
     lib.pinn_fit_steps_graph.restype = i32
     lib.pinn_fit_ctrl_bytes.restype = ctypes.c_size_t
+    # the optimizer family: the Adam entry points with `const pinn_optim_t*` in place of (lr, beta1, beta2, eps)
+    op = ctypes.POINTER(Optim)
+    lib.pinn_optim_step.argtypes = [vp, vp, vp, vp, vp, i64, vp, op, vp]
+    lib.pinn_optim_step_at.argtypes = [vp, vp, vp, vp, vp, i64, vp, i32, op, vp, i32, vp]
+    lib.pinn_residual_optim_step.argtypes = [vp, ctypes.POINTER(Residual), vp, vp, i64, ip, i32, i32, vp, f32, vp, vp, vp, vp,
+                                             vp, i32, op, vp, vp, ctypes.c_size_t, vp]
+    lib.pinn_fit_steps_optim.argtypes = [vp, ctypes.POINTER(Residual), vp, vp, i64, ip, ctypes.POINTER(f32), ctypes.POINTER(f32),
+                                         ctypes.c_uint64, ctypes.c_uint64, ip, i32, i32, f32, vp, vp, vp, vp, vp, i32, op,
+                                         vp, i32, vp, ctypes.c_size_t, vp]
+    lib.pinn_fit_steps_optim_graph.argtypes = lib.pinn_fit_steps_optim.argtypes[:-1] + [vp, ctypes.c_size_t, vp]
+    for name in ('pinn_optim_step', 'pinn_optim_step_at', 'pinn_residual_optim_step', 'pinn_fit_steps_optim', 'pinn_fit_steps_optim_graph'):
+        getattr(lib, name).restype = i32
     lib.pinn_set_tanh_mode.argtypes = [vp, i32]
     lib.pinn_set_tanh_mode.restype = i32
     lib.pinn_set_gemm_mode.argtypes = [vp, i32]
@@ -159,6 +188,7 @@ ABI_SYMBOLS = ('pinn_create', 'pinn_create_ex', 'pinn_destroy', 'pinn_layout', '
                'pinn_jet_backward', 'pinn_residual_step', 'pinn_residual_step_add', 'pinn_residual_adam_step', 'pinn_adam_step', 'pinn_adam_step_at', 'pinn_sample_points', 'pinn_fit_steps', 'pinn_fit_steps_graph', 'pinn_fit_ctrl_bytes', 'pinn_set_gemm_mode', 'pinn_set_tanh_mode', 'pinn_profile_tile',
                'pinn_last_tile_ms', 'pinn_last_wgrad_ms', 'pinn_last_kernel_name', 'pinn_last_wgrad_kernel_name', 'pinn_debug_last_kernel',
                'pinn_debug_prepass_in_kernel', 'pinn_debug_wgx_chunk_bytes', 'pinn_debug_max_wgs_per_cu', 'pinn_debug_fit_persistent', 'pinn_fit_chunk_status', 'pinn_set_act_params', 'pinn_debug_fit_onecu_rounds', 'pinn_debug_fit_graph_stats', 'pinn_last_launch_info',
+               'pinn_optim_step', 'pinn_optim_step_at', 'pinn_residual_optim_step', 'pinn_fit_steps_optim', 'pinn_fit_steps_optim_graph',
                'pinn_last_error', 'pinn_backend')
 
 _LIB = None
@@ -388,15 +418,24 @@ class Net:
 
     def residual_adam_step(self, residual, params, xs, grads, workspace, exp_avg, exp_avg_sq, mask, step_tensor, step,
                            lr, betas=(0.9, 0.999), eps=1e-8, dir_cols=(), n2=0, ic_streams=None, ic_const=0.0,
-                           loss_out=None, stream=None):
+                           loss_out=None, stream=None, optim=None):
         """ `loss_out`: device ADDRESS (int) that also receives the loss of the step; `stream`: handle from `stream_of`
-        when the caller has looked it up already (a fit loop asks once, not per iteration). """
+        when the caller has looked it up already (a fit loop asks once, not per iteration); `optim`: an `Optim` -- the update
+        rule of pinn_residual_optim_step instead of plain Adam's (lr, betas, eps) """
         for t, name in ((params, 'params'), (xs, 'xs'), (grads, 'grads'), (ic_streams, 'ic_streams'),
                         (exp_avg, 'exp_avg'), (exp_avg_sq, 'exp_avg_sq')):
             _check(t, name)
         _check(mask, 'mask', torch.uint8)
         _check(step_tensor, 'step', torch.int32)
         dirs, nd = self._dirs(dir_cols)
+        if optim is not None:
+            with _on_device(params):
+                self._raise(self.lib.pinn_residual_optim_step(
+                    self.handle, ctypes.byref(residual), _ptr(params), _ptr(xs), xs.shape[0], dirs, nd, n2, _ptr(ic_streams),
+                    float(ic_const), _ptr(grads), _ptr(exp_avg), _ptr(exp_avg_sq), _ptr(mask), _ptr(step_tensor), int(step),
+                    ctypes.byref(optim), None if loss_out is None else ctypes.c_void_p(loss_out), _ptr(workspace),
+                    workspace.numel() * workspace.element_size(), _stream(xs) if stream is None else stream))
+            return
         with _on_device(params):
             self._raise(self.lib.pinn_residual_adam_step(
                 self.handle, ctypes.byref(residual), _ptr(params), _ptr(xs), xs.shape[0], dirs, nd, n2, _ptr(ic_streams),
@@ -406,7 +445,8 @@ class Net:
                 workspace.numel() * workspace.element_size(), _stream(xs) if stream is None else stream))
 
     def fit_steps(self, residual, params, xs, columns, seed, call_index0, grads, workspace, exp_avg, exp_avg_sq, mask,
-                  step_tensor, step0, lr, betas, eps, loss_history, k_steps, dir_cols=(), n2=0, ic_const=0.0, stream=None, ctrl=None):
+                  step_tensor, step0, lr, betas, eps, loss_history, k_steps, dir_cols=(), n2=0, ic_const=0.0, stream=None, ctrl=None,
+                  optim=None):
         """ `k_steps` iterations of the fit loop (sample -> fused step -> Adam) enqueued by one call (include/pinn.h
         pinn_fit_steps); `xs` is the [N, d] batch buffer every iteration overwrites, `loss_history` a float32 device tensor
         with at least k_steps entries. """
@@ -422,12 +462,20 @@ class Net:
         a = (ctypes.c_float * d)(*[float(c[1]) for c in columns])
         b = (ctypes.c_float * d)(*[float(c[2]) for c in columns])
         dirs, nd = self._dirs(dir_cols)
+        # (`optim`: the update rule of pinn_fit_steps_optim / _optim_graph instead of plain Adam's lr, betas, eps)
+        rule = (float(lr), float(betas[0]), float(betas[1]), float(eps)) if optim is None else (ctypes.byref(optim), )
         common = (self.handle, ctypes.byref(residual), _ptr(params), _ptr(xs), xs.shape[0], kind, a, b,
                   int(seed) & (2 ** 64 - 1), int(call_index0), dirs, nd, n2, float(ic_const), _ptr(grads), _ptr(exp_avg),
-                  _ptr(exp_avg_sq), _ptr(mask), _ptr(step_tensor), int(step0), float(lr), float(betas[0]), float(betas[1]),
-                  float(eps), _ptr(loss_history), int(k_steps), _ptr(workspace), workspace.numel() * workspace.element_size())
+                  _ptr(exp_avg_sq), _ptr(mask), _ptr(step_tensor), int(step0), *rule,
+                  _ptr(loss_history), int(k_steps), _ptr(workspace), workspace.numel() * workspace.element_size())
         with _on_device(params):
-            if ctrl is not None:
+            if optim is not None:
+                if ctrl is not None:
+                    self._raise(self.lib.pinn_fit_steps_optim_graph(*common, _ptr(ctrl), ctrl.numel() * ctrl.element_size(),
+                                                                    _stream(xs) if stream is None else stream))
+                else:
+                    self._raise(self.lib.pinn_fit_steps_optim(*common, _stream(xs) if stream is None else stream))
+            elif ctrl is not None:
                 # `ctrl`: a uint8 device tensor of pinn_fit_ctrl_bytes() bytes -- the chunk as one replayable launch graph
                 # (pinn_fit_steps_graph; the library falls back to the eager loop by itself where a graph does not apply)
                 self._raise(self.lib.pinn_fit_steps_graph(*common, _ptr(ctrl), ctrl.numel() * ctrl.element_size(),
@@ -470,3 +518,19 @@ class Net:
             self._raise(self.lib.pinn_adam_step(_ptr(params), _ptr(grads), _ptr(exp_avg), _ptr(exp_avg_sq), _ptr(mask),
                                                 params.numel(), _ptr(step), float(lr), float(betas[0]), float(betas[1]),
                                                 float(eps), _stream(params)))
+
+    def optim_step(self, params, grads, exp_avg, exp_avg_sq, mask, step, optim, at=0, loss_out=None, stream=None):
+        """ `adam_step` with the update rule of `optim` (an `Optim`; include/pinn.h pinn_optim_step / pinn_optim_step_at) """
+        for t, name in ((params, 'params'), (grads, 'grads'), (exp_avg, 'exp_avg'), (exp_avg_sq, 'exp_avg_sq')):
+            _check(t, name)
+        _check(mask, 'mask', torch.uint8)
+        _check(step, 'step', torch.int32)
+        with _on_device(params):
+            if at > 0:
+                self._raise(self.lib.pinn_optim_step_at(_ptr(params), _ptr(grads), _ptr(exp_avg), _ptr(exp_avg_sq), _ptr(mask),
+                                                        params.numel(), _ptr(step), int(at), ctypes.byref(optim),
+                                                        None if loss_out is None else ctypes.c_void_p(loss_out),
+                                                        int(self.layout.off_loss), _stream(params) if stream is None else stream))
+            else:
+                self._raise(self.lib.pinn_optim_step(_ptr(params), _ptr(grads), _ptr(exp_avg), _ptr(exp_avg_sq), _ptr(mask),
+                                                     params.numel(), _ptr(step), ctypes.byref(optim), _stream(params)))

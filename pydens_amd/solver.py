@@ -31,17 +31,66 @@ from .tokens import current_model
 UNSET = object()        # Solver._imap outside a step: a custom forward()'s input map has not been asked for
 
 
-class FlatAdam:
-    """ torch.optim.Adam semantics (reference model_torch.py:419-422, :461) on the flat kernel buffer. """
-    def __init__(self, model, lr=0.005, betas=(0.9, 0.999), eps=1e-8, weight_decay=0, amsgrad=False, **kwargs):
-        if weight_decay != 0 or amsgrad or kwargs:
-            raise NotImplementedError('the HIP Adam kernel implements plain Adam (lr, betas, eps); got '
-                                      f'weight_decay={weight_decay}, amsgrad={amsgrad}, {kwargs}')
-        self.model, self.lr, self.betas, self.eps = model, lr, betas, eps
+class FlatOptimizer:
+    """ torch.optim semantics (reference model_torch.py:419-422, :461) on the flat kernel buffer for the rules the kernels carry
+    (include/pinn.h pinn_optim_t): Adam and AdamW with weight decay, SGD, RMSprop -- two state arrays at most, the model's two moment
+    buffers. `exp_avg` / `exp_avg_sq` name those buffers for every rule; the torch names of what a rule keeps in them are aliases. """
+    # rule -> (code, the keywords it takes besides lr)
+    RULES = {'Adam': (engine.OPT_ADAM, ('betas', 'eps', 'weight_decay')),
+             'AdamW': (engine.OPT_ADAMW, ('betas', 'eps', 'weight_decay')),
+             'SGD': (engine.OPT_SGD, ('momentum', 'dampening', 'nesterov', 'weight_decay')),
+             'RMSprop': (engine.OPT_RMSPROP, ('alpha', 'eps', 'weight_decay', 'momentum', 'centered'))}
+
+    @classmethod
+    def hyper(cls, name, lr, kwargs):
+        """ the hyper-parameters torch resolves for `getattr(torch.optim, name)(params, lr=lr, **kwargs)` -- torch's own argument checks raise
+        here as they do there -- if the kernels carry that call, else None: another name, another keyword (amsgrad, maximize, foreach,
+        capturable, fused, differentiable), a tensor where torch also takes a number, RMSprop with momentum AND centered (three arrays) """
+        if name not in cls.RULES or set(kwargs) - set(cls.RULES[name][1]):
+            return None
+        number = lambda v: isinstance(v, (int, float)) and not isinstance(v, bool)
+        values = [lr] + [v for key, v in kwargs.items() if key not in ('betas', 'nesterov', 'centered')]
+        betas = kwargs.get('betas', (0.0, 0.0))
+        if not all(number(v) for v in values) or not (isinstance(betas, (tuple, list)) and len(betas) == 2 and all(number(b) for b in betas)):
+            return None
+        hyper = getattr(torch.optim, name)([torch.zeros(1, requires_grad=True)], lr=lr, **kwargs).defaults
+        if name == 'RMSprop' and hyper['momentum'] > 0 and hyper['centered']:
+            return None
+        return {key: hyper[key] for key in ('lr', ) + cls.RULES[name][1]}
+
+    def __init__(self, model, name, lr=0.005, **kwargs):
+        hyper = self.hyper(name, lr, kwargs)
+        if hyper is None:
+            raise NotImplementedError(f'the HIP optimizer kernels do not carry torch.optim.{name}(lr={lr}, **{kwargs})')
+        self.name, self.hyper_parameters = name, hyper
+        self.torch_kwargs = dict(kwargs)            # (what `TorchOptimizerAdapter.continuing` hands torch.optim)
+        self.optim = engine.Optim.build(self.RULES[name][0], **hyper)       # None: plain Adam through the Adam entry points (FlatAdam)
+        self.model, self.lr = model, hyper['lr']
+        self.betas, self.eps = tuple(hyper.get('betas', (0.0, 0.0))), hyper.get('eps', 0.0)
+        self._take_state(model)
+
+    # what the two buffers hold under a rule, by torch's names (torch.optim state keys)
+    STATE_KEYS = {'Adam': ('exp_avg', 'exp_avg_sq'), 'AdamW': ('exp_avg', 'exp_avg_sq'), 'SGD': ('momentum_buffer', None)}
+
+    def state_keys(self):
+        """ (torch's state key of the first buffer, of the second); None: the rule does not use that buffer """
+        if self.name == 'RMSprop':
+            hyper = self.hyper_parameters
+            return ('momentum_buffer' if hyper['momentum'] > 0 else ('grad_avg' if hyper['centered'] else None), 'square_avg')
+        if self.name == 'SGD':
+            return ('momentum_buffer' if self.hyper_parameters['momentum'] != 0 else None, None)
+        return self.STATE_KEYS[self.name]
+
+    def __getattr__(self, key):
+        if key in ('momentum_buffer', 'grad_avg', 'square_avg') and key in self.state_keys():
+            return self.exp_avg if self.state_keys()[0] == key else self.exp_avg_sq
+        raise AttributeError(key)
+
+    def _take_state(self, model):
         # the moment buffers and the device step counter belong to the MODEL and are zeroed here: every fit call builds a fresh
         # optimizer (reference :419-422) -- at the same device addresses, so that the launch graph a previous fit call recorded
         # (pinn_fit_steps_graph keys on the addresses its nodes carry) is replayed instead of re-recorded (ADVICE r4). One live
-        # FlatAdam per model: the Solver never keeps an old one.
+        # optimizer per model: the Solver never keeps an old one.
         state = getattr(model, '_adam_state', None)
         if state is None or state[0].shape != model.flat.shape or state[0].device != model.flat.device:
             state = model._adam_state = (torch.zeros_like(model.flat), torch.zeros_like(model.flat),
@@ -99,6 +148,24 @@ class FlatAdam:
     def step(self, grads, loss_out=None, stream=None):
         """ loss_out: device address that receives grads[off_loss] in the same launch (the fit's loss history) """
         self.t += 1
+        self.model.net.optim_step(self.model.flat, grads, self.exp_avg, self.exp_avg_sq, self.mask, self.step_count, self.optim,
+                                  at=self.t, loss_out=loss_out, stream=stream)
+
+
+class FlatAdam(FlatOptimizer):
+    """ plain torch.optim.Adam (lr, betas, eps): the default of `Solver.fit`, through the Adam entry points of the library """
+    def __init__(self, model, lr=0.005, betas=(0.9, 0.999), eps=1e-8, weight_decay=0, amsgrad=False, **kwargs):
+        if weight_decay != 0 or amsgrad or kwargs:
+            raise NotImplementedError('FlatAdam is plain Adam (lr, betas, eps); got '
+                                      f'weight_decay={weight_decay}, amsgrad={amsgrad}, {kwargs}')
+        self.name, self.optim = 'Adam', None
+        self.hyper_parameters = dict(lr=lr, betas=betas, eps=eps, weight_decay=0)
+        self.torch_kwargs = dict(betas=betas, eps=eps)
+        self.model, self.lr, self.betas, self.eps = model, lr, betas, eps
+        self._take_state(model)
+
+    def step(self, grads, loss_out=None, stream=None):
+        self.t += 1
         self.model.net.adam_step(self.model.flat, grads, self.exp_avg, self.exp_avg_sq, self.mask, self.step_count,
                                  self.lr, self.betas, self.eps, at=self.t, loss_out=loss_out, stream=stream)
 
@@ -111,20 +178,32 @@ class TorchOptimizerAdapter:
         self.params = model.optimizer_parameters()
         self.opt = getattr(torch.optim, name)(self.params, lr=lr, **kwargs)
 
+    @property
+    def name(self):
+        return type(self.opt).__name__
+
     @classmethod
-    def continuing(cls, adam):
-        """ torch.optim.Adam carrying on where a FlatAdam stands: same members, moments and -- per parameter -- step counts (FlatAdam.lagging) """
-        model = adam.model
+    def continuing(cls, flat):
+        """ the torch optimizer of a FlatOptimizer's rule carrying on where it stands: same members, hyper-parameters, state arrays and -- per
+        parameter -- step counts (FlatOptimizer.lagging); a parameter never stepped has no state (SGD: no momentum buffer yet) """
+        model = flat.model
         self = cls.__new__(cls)
         self.model = model
-        members = adam.members
+        members = flat.members
         self.params = [p for p in model.parameters() if bool(members.as_strided(tuple(p.shape), tuple(p.stride()), p.storage_offset()).any())]
-        self.opt = torch.optim.Adam(self.params, lr=adam.lr, betas=adam.betas, eps=adam.eps)
+        self.opt = getattr(torch.optim, flat.name)(self.params, lr=flat.lr, **flat.torch_kwargs)
+        first, second = flat.state_keys()
         for p in self.params:
-            steps = adam.steps_of(p.storage_offset()) if p.numel() == 1 else adam.t
+            steps = flat.steps_of(p.storage_offset()) if p.numel() == 1 else flat.t
             if steps > 0:
                 view = lambda buf: buf.as_strided(tuple(p.shape), tuple(p.stride()), p.storage_offset()).clone()
-                self.opt.state[p] = {'step': torch.tensor(float(steps)), 'exp_avg': view(adam.exp_avg), 'exp_avg_sq': view(adam.exp_avg_sq)}
+                state = {} if flat.name == 'SGD' else {'step': torch.tensor(float(steps))}
+                if first is not None:
+                    state[first] = view(flat.exp_avg)
+                if second is not None:
+                    state[second] = view(flat.exp_avg_sq)
+                if state:
+                    self.opt.state[p] = state
         return self
 
     def refresh(self):
@@ -169,6 +248,10 @@ class Solver:
         if os.environ.get('PYDENS_AMD_CRITERION'):
             self.set_criterion_path(os.environ['PYDENS_AMD_CRITERION'])
         self.optimizer = None
+        self.optimizer_path = 'torch'       # set_optimizer_path: optimizers other than plain Adam as torch.optim code or on the fused kernels
+        self.last_fit_optimizer = None
+        if os.environ.get('PYDENS_AMD_OPTIMIZER'):
+            self.set_optimizer_path(os.environ['PYDENS_AMD_OPTIMIZER'])
 
         self.model = model(**kwargs, ndims=ndims, initial_condition=initial_condition,
                            boundary_condition=boundary_condition, domain=domain, nparams=nparams)
@@ -231,6 +314,19 @@ class Solver:
         if path not in self.CRITERION_PATHS:
             raise ValueError(f'criterion path {path!r}: expected one of {sorted(self.CRITERION_PATHS)}')
         self.criterion_path = path
+
+    OPTIMIZER_PATHS = ('torch', 'fused')
+
+    def set_optimizer_path(self, path):
+        """ where `fit(optimizer=...)` other than plain Adam runs: 'torch' (default: torch.optim updates views of the flat buffer, a train of
+        launches behind the gradient reduction) or 'fused' -- Adam and AdamW with weight decay, SGD (momentum, dampening, nesterov, weight
+        decay) and RMSprop (alpha, weight decay, momentum OR centered) are applied by the kernels (include/pinn.h pinn_optim_t): in the
+        gradient reduction's launch, in the fit chunks and their launch graphs, in the one-CU chunk kernel. Matched by exact name and
+        keywords; anything else (amsgrad, maximize, ..., other optimizers) stays on torch.optim in either setting.
+        `last_fit_optimizer` tells, e.g. 'AdamW/fused'. Process-wide: PYDENS_AMD_OPTIMIZER. """
+        if path not in self.OPTIMIZER_PATHS:
+            raise ValueError(f'optimizer path {path!r}: expected one of {sorted(self.OPTIMIZER_PATHS)}')
+        self.optimizer_path = path
 
     def _lower_criterion(self, criterion):
         """ (code, parameter, sum) of a criterion the point stage has in closed form, else None. By EXACT type: a subclass may override
@@ -886,8 +982,12 @@ class Solver:
         if optimizer is not None:                                                          # :419-422
             plain_adam = optimizer == 'Adam' and not kwargs.get('weight_decay') and not kwargs.get('amsgrad') and \
                 not (set(kwargs) - {'betas', 'eps', 'weight_decay', 'amsgrad'})
-            self.optimizer = (FlatAdam(model, lr=lr, **kwargs) if plain_adam
-                              else TorchOptimizerAdapter(model, optimizer, lr, **kwargs))
+            if plain_adam:
+                self.optimizer = FlatAdam(model, lr=lr, **kwargs)
+            elif self.optimizer_path == 'fused' and FlatOptimizer.hyper(optimizer, lr, kwargs) is not None:
+                self.optimizer = FlatOptimizer(model, optimizer, lr=lr, **kwargs)
+            else:
+                self.optimizer = TorchOptimizerAdapter(model, optimizer, lr, **kwargs)
         elif self.optimizer is None:
             raise ValueError('optimizer=None reuses the optimizer of a previous fit call; there is none yet')
         self._generic_graph = None          # launch graphs of the generic step are recorded per fit call (closure constants may have changed)
@@ -896,9 +996,11 @@ class Solver:
         nums_constraints = [int(term.replace('constraint', '').replace('_', ''))
                             for term in loss_terms if 'constraint' in term]
         self._refresh_traces(set(nums_constraints))
-        if isinstance(self.optimizer, FlatAdam) and model.variables:
+        if isinstance(self.optimizer, FlatOptimizer) and (model.variables or not isinstance(self.optimizer, FlatAdam)):
             # (trainable V(...) scalars: which of them the terms of THIS call reach decides what torch's Adam does with them; one dry
-            #  evaluation per fit call. Without variables nothing changes from call to call: log_scale is reached iff there is an IC)
+            #  evaluation per fit call. Without variables nothing changes from call to call: log_scale is reached iff there is an IC --
+            #  which plain Adam need not know, a zero gradient on fresh moments moves nothing; weight decay would move it, so the other
+            #  rules always ask)
             lay = model.net.layout
             scalars = [lay.off_log_scale] + [off + i for off, n in model.variables.values() for i in range(n)]
             self.optimizer.refresh(self._unreached_scalars(scalars, loss_terms, nums_constraints, criterion))
@@ -931,7 +1033,8 @@ class Solver:
         self.last_fit_path = 'fused' if fused else 'generic'
         self.last_fit_criterion = f'{type(criterion).__name__}/{self.last_fit_path}'
         self._apply_criterion(crit if fused else (engine.CRIT_MSE, 0.0, False), nums_constraints)
-        flat_adam = isinstance(self.optimizer, FlatAdam)
+        flat_adam = isinstance(self.optimizer, FlatOptimizer)       # (any rule of the kernels; FlatAdam is the default one)
+        self.last_fit_optimizer = f"{self.optimizer.name}/{'fused' if flat_adam else 'torch'}"
         one_launch = fused and world == 1 and flat_adam and tuple(loss_terms) == ('equation',)
         stream = engine.stream_of(model.flat)           # looked up once per call, not per iteration
         history_ptr = history.data_ptr()
@@ -1022,7 +1125,7 @@ class Solver:
                     model.net.fit_steps(self.program, model.flat, xs, columns, seed, call0, self.grads, ws, adam.exp_avg,
                                         adam.exp_avg_sq, adam.mask, adam.step_count, adam.t + 1, adam.lr, adam.betas, adam.eps,
                                         history[it:it + k], k, dir_cols=spec.dir_cols, n2=n2, ic_const=model.kernel_ic_const(),
-                                        stream=stream, ctrl=ctrl)
+                                        stream=stream, ctrl=ctrl, optim=adam.optim)
                     if os.environ.get('PYDENS_AMD_FIT_PERSIST') == '1' and model.net.lib.pinn_fit_chunk_status() != 0:
                         # the opt-in GRID form of the one-launch chunk gave up at its device-wide wait: nothing of the chunk was applied
                         # (include/pinn.h pinn_fit_chunk_status; the check synchronises with the device once per chunk)
@@ -1057,7 +1160,7 @@ class Solver:
             model.net.residual_adam_step(self.program, model.flat, xs, self.grads, ws, adam.exp_avg, adam.exp_avg_sq,
                                          adam.mask, adam.step_count, adam.t, adam.lr, adam.betas, adam.eps,
                                          dir_cols=spec.dir_cols, n2=n2, ic_streams=ic_streams,
-                                         ic_const=model.kernel_ic_const(), loss_out=loss_out, stream=stream)
+                                         ic_const=model.kernel_ic_const(), loss_out=loss_out, stream=stream, optim=adam.optim)
             return
         # data parallel: this rank's share of a GLOBAL batch (shares may differ by one point: the true global count divides)
         n_global = self._global_batch if (world > 1 and getattr(self, '_global_batch', None)) else xs.shape[0] * world
