@@ -25,6 +25,8 @@
 //   PINN_FAST_MT_S5 / _S2 / _COMB, PINN_FAST_VAR_COMB, PINN_WIDE_MT (pinn_inst.inc)   tile heights of the fast kernels
 //   PINN_SP_ROUND (2), PINN_SP_PIPE / PINN_SP_PIPE_W (per translation unit: build.py)   split-bf16 kernels
 //   PINN_TEAM_FLAGS (0)           team-local LDS arrival counters instead of s_barrier in the two-team kernels (measured slower)
+//   PINN_TEAM_ROW_LDS (1)         two-team kernels: the teams' gradient sums meet in LDS and leave as one coalesced partial row (0: team 0
+//                                 stores its row, team 1 reads it back from global memory and adds -- the same sums bit for bit)
 //   PINN_PTALL (round 5)          shape-specialised kernels: the point stage (ansatz, residual, their reverse) evaluated by EVERY lane for
 //                                 its own point (16 * MT points, replicated over the unit quads and the waves) instead of by the first T
 //                                 threads: the LDS round trip of the upstream gradient and the barrier behind the point stage disappear
@@ -2981,6 +2983,121 @@ PINN_DEVICE void pinn_tile_body(const PinnKArgs& A, const float* params_, float*
     (void)scal;
     PINN_SYNC();
     float* part = partials_ + (size_t)rowid * rstride_;
+    // Two-team kernels with W^T in LDS: the teams' sums meet in LDS and the row leaves ONCE, coalesced. Before, every lane of team 0 stored
+    // its 16 x LHC hidden-layer accumulator entries as single dwords (a wave's store: four 64-byte pieces of four rows), and a fence and a
+    // barrier later team 1 read them back from global memory, added its own and stored again: 12 K ticks at the end of every workgroup of
+    // BASELINE config 2 (profiles/r06_launch_fixed_cost.txt). The W^T block is dead behind the tile loop (the barrier above): team 0 lays its
+    // accumulators out there in the partial row's own [unit][input] order, team 1 adds on top -- the same single fp32 addition per entry,
+    // team 0's value + team 1's, as `row + value` was: bit for bit the row of before -- and all eight waves store whole rows as 16-byte pieces.
+    // The LDS-resident sums (bias rows, first-layer columns) are read from both teams' blocks where they are stored; the last-layer sums and
+    // the head scalars of team 1 cross through the words behind the rows. (Partial rows are 16-byte aligned: every offset of the layout is a
+    // multiple of four floats for widths that are multiples of 16, and the workspace is checked -- pinn_abi.cpp run_train.)
+    constexpr int ROW_LD = HP + 4;                           // (rows lq * 4 + r of a wave's ds_write: 16 banks apart)
+    constexpr int ROWS_FLOATS = (LHC > 0 ? LHC : 0) * HP * ROW_LD;
+#ifndef PINN_TEAM_ROW_LDS
+#define PINN_TEAM_ROW_LDS 1     // (0 in experiment / test builds: the teams meet in the partial row, one after the other)
+#endif
+    constexpr bool TEAM_MERGE = PINN_TEAM_ROW_LDS && TEAMS2 && WTL && !DWG && !VWG && LHC <= PINN_LHMAX &&
+                                (ROWS_FLOATS + HP + 8 + PINN_MAX_VARS <= (LHC > 0 ? LHC : 0) * HP * C::WT_LD);
+    if constexpr (TEAM_MERGE) {
+        float* rows = WTs;
+        float* xch_wl = WTs + ROWS_FLOATS;                   // team 1: [HP] last-layer sums, loss / log_scale / b_L, the V(...) slots
+        float* xch_sc = xch_wl + HP;
+        const bool prog_vars = PROG && SH::mode(A) == PINN_MODE_STEP && SH::res_kind(A) == PINN_RES_PROGRAM;
+        auto row_at = [&](int l, int o, int j, int r) -> float* {
+            return rows + (l * HP + o * 16 + lq * 4 + r) * ROW_LD + (wave * NTW + j) * 16 + lr;
+        };
+        float wl_sum[NTW][4];
+#pragma unroll
+        for (int j = 0; j < NTW; ++j)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) wl_sum[j][r] = pinn_row_sum16(accWL[j][r]);
+        float gvar[PINN_MAX_VARS];
+#pragma unroll
+        for (int k = 0; k < PINN_MAX_VARS; ++k) gvar[k] = 0.0f;
+        if (prog_vars && tid == 64 * ptw) {
+            const int vbase = S + d + A.n_aux;
+            for (int k = 0; k < A.n_vars; ++k) {
+                float g = 0.0f;
+                for (int i = 0; i < T; ++i) g += padj[(vbase + k) * T + i];
+                gvar[k] = g;
+            }
+        }
+        if (team == 0) {
+#pragma unroll
+            for (int l = 0; l < LHC; ++l)
+#pragma unroll
+                for (int o = 0; o < NT; ++o)
+#pragma unroll
+                    for (int j = 0; j < NTW; ++j)
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) *row_at(l, o, j, r) = dW[l][o][j][r];
+        } else {
+#pragma unroll
+            for (int j = 0; j < NTW; ++j)
+#pragma unroll
+                for (int r = 0; r < 4; ++r)
+                    if (lr == 0) xch_wl[unit0(j) + r] = wl_sum[j][r];
+            if (tid == 64 * ptw) {
+                xch_sc[0] = tot_loss; xch_sc[1] = tot_ls; xch_sc[2] = tot_bl;
+#pragma unroll
+                for (int k = 0; k < PINN_MAX_VARS; ++k) xch_sc[8 + k] = gvar[k];
+            }
+        }
+        PINN_SYNC();
+        if (team == 1) {
+#pragma unroll
+            for (int l = 0; l < LHC; ++l)
+#pragma unroll
+                for (int o = 0; o < NT; ++o) {
+                    // (a tile row's reads first, then its writes: sixteen round trips in flight instead of one)
+                    float old[NTW][4];
+#pragma unroll
+                    for (int j = 0; j < NTW; ++j)
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) old[j][r] = *row_at(l, o, j, r);
+#pragma unroll
+                    for (int j = 0; j < NTW; ++j)
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) *row_at(l, o, j, r) = old[j][r] + dW[l][o][j][r];
+                }
+        } else {
+            // team 0 meanwhile: the small entries, its own value + team 1's
+#pragma unroll
+            for (int j = 0; j < NTW; ++j)
+#pragma unroll
+                for (int r = 0; r < 4; ++r)
+                    if (lr == 0) part[A.off_wl + unit0(j) + r] = wl_sum[j][r] + xch_wl[unit0(j) + r];
+            if (tid == 64 * ptw) {
+                part[A.off_loss] = tot_loss + xch_sc[0];
+                part[A.off_ls] = tot_ls + xch_sc[1];
+                part[A.off_bl] = tot_bl + xch_sc[2];
+                for (int i = A.off_loss + 1; i < A.p_core; ++i) part[i] = 0.0f;
+                if (prog_vars)
+                    for (int k = 0; k < A.n_vars; ++k) part[A.off_extra + k] = gvar[k] + xch_sc[8 + k];
+            }
+        }
+        PINN_SYNC();
+        const float* accB_0 = smem_all + C::O_ACCB, * accB_1 = accB_0 + TEAM_FLOATS;
+        const float* accW1_0 = smem_all + C::O_ACCW1, * accW1_1 = accW1_0 + TEAM_FLOATS;
+#pragma unroll
+        for (int l = 0; l < LHC; ++l) {
+            float* dst = part + A.off_wh + (size_t)l * A.hidden_stride;
+            for (int i = gtid; i < HP * HP / 4; i += NTH_ALL) {
+                const int n = i / (HP / 4), c = (i % (HP / 4)) * 4;
+                pinn_st4(dst + n * HP + c, pinn_ld4(rows + (l * HP + n) * ROW_LD + c));
+            }
+        }
+        for (int i = gtid; i < (lh + 1) * HP; i += NTH_ALL) {
+            const int a_ = i / HP, n = i % HP;
+            const int dst = (a_ == 0) ? A.off_b1 + n : A.off_wh + (a_ - 1) * A.hidden_stride + HP * HP + n;
+            part[dst] = accB_0[i] + accB_1[i];
+        }
+        for (int i = gtid; i < HP * d; i += NTH_ALL) {
+            const int e = (i / d) * PINN_XS_LD + (i % d);
+            part[i] = accW1_0[e] + accW1_1[e];
+        }
+    } else
     for (int round = 0; round < (VWG ? 1 : TEAMS); ++round) {
         if (VWG || team == round) {
             const bool add = round > 0;
