@@ -334,6 +334,13 @@ int pinn_optim_step(float* params, const float* grads, float* exp_avg, float* ex
                     int32_t* step_ptr, const pinn_optim_t* opt, void* stream);
 int pinn_optim_step_at(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, const uint8_t* mask, int64_t n,
                        int32_t* step_ptr, int32_t step, const pinn_optim_t* opt, float* loss_out, int32_t off_loss, void* stream);
+/* The launch behind the tile kernel on rows of the caller's: grads[i] = (accumulate ? grads[i] : 0) + sum over the n_rows rows of
+ * partials[row * row_len + i] -- in the fixed order of every fused step (rows r, r + 32, r + 64, ... in double for r = 0 .. 31, those 32
+ * sums in ascending r, the old gradient last, one rounding) -- and, with `opt` non-NULL, the update of pinn_optim_step_at in the same
+ * launch (loss_out, when given, receives the summed entry off_loss). opt NULL: the sum alone; params .. step are not read. */
+int pinn_reduce_rows(const float* partials, int32_t n_rows, int32_t row_len, float* grads, int accumulate, float* params, float* exp_avg,
+                     float* exp_avg_sq, const uint8_t* mask, int32_t* step_ptr, int32_t step, const pinn_optim_t* opt, float* loss_out,
+                     int32_t off_loss, void* stream);
 /* pinn_residual_adam_step, pinn_fit_steps and pinn_fit_steps_graph with the rule of `opt` (the Adam entry points are these with a plain-Adam
  * struct). The launch-graph cache of pinn_fit_steps_optim_graph keys on the whole struct. */
 int pinn_residual_optim_step(pinn_t* net, const pinn_residual_t* residual, float* params, const float* xs,
@@ -413,6 +420,9 @@ const char* pinn_last_kernel_name(void);
 /* ... and of the streamed weight-gradient kernel of widths >= 128 ("" before the first such launch); the last template argument
  * says whether it was the split-bf16 form (pinn_set_gemm_mode) */
 const char* pinn_last_wgrad_kernel_name(void);
+/* ... and of the last reduction launch: "pinn_reduce_kernel" (16-byte row loads) or "pinn_reduce_scalar_kernel" (rows that are not
+ * 16-byte aligned: base or row length); "" before the first */
+const char* pinn_last_reduce_kernel_name(void);
 /* Geometry of the last tile-kernel launch: out[0] = workgroups of the grid, out[1] = workgroups per CU the grid was planned with
  * (what hipOccupancyMaxActiveBlocksPerMultiprocessor answered for the instantiation, capped -- see pinn_debug_max_wgs_per_cu),
  * out[2] = threads per workgroup, out[3] = bytes of dynamic LDS. The large-batch parity tests assert with it that they really

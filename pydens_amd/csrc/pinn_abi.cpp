@@ -392,27 +392,41 @@ static void optim_scalars(const PinnOptK& k, double step, float* step_size, floa
     if (k.rule == PINN_OPT_ADAM || k.rule == PINN_OPT_ADAMW) pinn_adam_scalars(step, k.lr, k.b1, k.b2, step_size, bc2_sqrt);
 }
 
+// which form of the reduction the last launch_reduce took (pinn_last_reduce_kernel_name)
+const char* g_last_reduce_name = "";
+
+// The 16-byte row loads of pinn_reduce_kernel need every row to start on a 16-byte boundary: a base aligned to 16 bytes and a row stride
+// that is a multiple of 4 floats. pinn_create_ex's layout guarantees the stride for the library's own launches (p_total = hp (d + 2) +
+// lh (hp hp + hp) + 4 + PINN_EXTRA_SLOTS with hp a multiple of 16 and 16 user slots: a multiple of 4 for every net), and fill_args puts
+// the partial rows at the very start of the caller's workspace, which run_train refuses unless it is 16-byte aligned: every fused step
+// takes the vector form. pinn_reduce_rows takes any base and any row length: rows that do not qualify take the scalar form (same sums,
+// pinn_aux_kernels.h). -DPINN_REDUCE_SCALAR=1 rebuilds the library
+// with the scalar form everywhere, for the A/B.
+#ifndef PINN_REDUCE_SCALAR
+#define PINN_REDUCE_SCALAR 0
+#endif
 int launch_reduce(const float* partials, int n_wg, int p_core, float* grads, int accumulate, void* stream,
                   const AdamArgs* adam = nullptr) {
-    const int blocks = (p_core + PINN_REDUCE_PB - 1) / PINN_REDUCE_PB;
-    const size_t smem = 1024 * sizeof(double);      // (the chunk sums cross the LDS in double: pinn_reduce_kernel)
+    const bool vec = !PINN_REDUCE_SCALAR && p_core % 4 == 0 && (reinterpret_cast<uintptr_t>(partials) & 15) == 0;
+    const int lc = vec ? PINN_REDUCE_LC : PINN_REDUCE_SCALAR_LC, pb = vec ? 4 * lc : lc, threads = lc * PINN_REDUCE_CH;
+    const int blocks = (p_core + pb - 1) / pb;
+    const size_t smem = (size_t)PINN_REDUCE_CH * pb * sizeof(double);      // (the chunk sums cross the LDS in double: [CH][PB])
     AdamArgs z = {nullptr, nullptr, nullptr, nullptr, nullptr, 0, plain_adam(0.f, 0.f, 0.f, 0.f), nullptr, -1};
     const AdamArgs& a = adam ? *adam : z;
     const int do_adam = adam ? 1 : 0;
     float step_size = 0.0f, bc2_sqrt = 1.0f;
     if (adam) optim_scalars(a.opt, (double)a.step_value, &step_size, &bc2_sqrt);
+    PinnReduceArgs ra = {partials, n_wg, p_core, grads, accumulate, do_adam, a.params, a.m, a.v, a.mask, a.step_value, step_size, bc2_sqrt,
+                         a.opt, a.step_ptr, a.loss_out, a.off_loss, nullptr, 0,
+                         do_adam ? g_fit_next : PinnNextBatch{nullptr, 0, {}, 0u, 0u, 0ull}};
+    g_last_reduce_name = vec ? "pinn_reduce_kernel" : "pinn_reduce_scalar_kernel";
 #ifdef PINN_EMU
-    emu::launch(blocks, 1024, smem, [&] {
-        pinn_reduce_kernel(partials, n_wg, p_core, grads, accumulate, do_adam, a.params, a.m, a.v, a.mask, a.step_value,
-                           step_size, bc2_sqrt, a.opt, a.step_ptr, a.loss_out, a.off_loss, nullptr, 0,
-                           do_adam ? g_fit_next : PinnNextBatch{nullptr, 0, {}, 0u, 0u, 0ull});
-    });
+    if (vec) emu::launch(blocks, threads, smem, [&] { pinn_reduce_kernel(ra); });
+    else emu::launch(blocks, threads, smem, [&] { pinn_reduce_scalar_kernel(ra); });
 #else
-    const PinnFitCtrl* ctrl = do_adam ? g_fit_capture.ctrl : nullptr;
-    hipLaunchKernelGGL(pinn_reduce_kernel, dim3(blocks), dim3(1024), smem, (hipStream_t)stream, partials, n_wg, p_core,
-                       grads, accumulate, do_adam, a.params, a.m, a.v, a.mask, a.step_value, step_size, bc2_sqrt, a.opt,
-                       a.step_ptr, a.loss_out, a.off_loss, ctrl, g_fit_capture.k,
-                       do_adam ? g_fit_next : PinnNextBatch{nullptr, 0, {}, 0u, 0u, 0ull});
+    if (do_adam) { ra.ctrl = g_fit_capture.ctrl; ra.ctrl_k = g_fit_capture.k; }
+    if (vec) hipLaunchKernelGGL(pinn_reduce_kernel, dim3(blocks), dim3(threads), smem, (hipStream_t)stream, ra);
+    else hipLaunchKernelGGL(pinn_reduce_scalar_kernel, dim3(blocks), dim3(threads), smem, (hipStream_t)stream, ra);
     if (hipGetLastError() != hipSuccess) return fail("reduce kernel launch failed");
 #endif
     return 0;
@@ -505,6 +519,8 @@ int pinn_set_gemm_mode(pinn_t* net, int mode) {
 const char* pinn_last_kernel_name(void) { return g_pinn_last_kernel_name; }
 
 const char* pinn_last_wgrad_kernel_name(void) { return g_pinn_last_wgrad_name; }
+
+const char* pinn_last_reduce_kernel_name(void) { return g_last_reduce_name; }
 
 int pinn_debug_prepass_in_kernel(pinn_t* net, int enable) {
     if (!net) return fail("null argument");
@@ -1432,6 +1448,24 @@ int pinn_optim_step_at(float* params, const float* grads, float* exp_avg, float*
     if (step < 1) return fail("step must be >= 1");
     if (loss_out && (off_loss < 0 || off_loss >= n)) return fail("off_loss=%d outside the gradient buffer", off_loss);
     return optim_launch(params, grads, exp_avg, exp_avg_sq, mask, n, step_ptr, step, k, stream, loss_out, off_loss);
+}
+
+int pinn_reduce_rows(const float* partials, int32_t n_rows, int32_t row_len, float* grads, int accumulate, float* params, float* exp_avg,
+                     float* exp_avg_sq, const uint8_t* mask, int32_t* step_ptr, int32_t step, const pinn_optim_t* opt, float* loss_out,
+                     int32_t off_loss, void* stream) {
+    if (!partials || !grads) return fail("null argument");
+    if (n_rows < 1 || row_len < 1) return fail("n_rows=%d, row_len=%d: both must be >= 1", n_rows, row_len);
+    if (loss_out && (off_loss < 0 || off_loss >= row_len)) return fail("off_loss=%d outside the gradient buffer", off_loss);
+    if (!opt) {
+        if (loss_out) return fail("loss_out rides in the update's launch: it needs an optimizer description");
+        return launch_reduce(partials, n_rows, row_len, grads, accumulate ? 1 : 0, stream);
+    }
+    PinnOptK k;
+    if (optim_prepare(opt, &k)) return 1;
+    if (!params || !exp_avg || !exp_avg_sq || !step_ptr) return fail("null argument");
+    if (step < 1) return fail("step must be >= 1");
+    AdamArgs adam = {params, exp_avg, exp_avg_sq, mask, step_ptr, step, k, loss_out, loss_out ? off_loss : -1};
+    return launch_reduce(partials, n_rows, row_len, grads, accumulate ? 1 : 0, stream, &adam);
 }
 
 }  // extern "C"

@@ -24,9 +24,8 @@ pinn_aux_kernel(const float* xs, long long n, int d, pinn_program_t pg, PinnPreC
 }
 
 // ------------------------------------------------------------------------------------------------------------
-// sum of the per-workgroup partial gradients (fixed order => deterministic): block = 64 parameters x 16 chunks of
-// workgroups (every wave reads whole 256-B rows), LDS tree over the chunks; optionally the Adam update of those 64
-// parameters right behind it (single-rank steps: no all-reduce in between, two launches less).
+// sum of the per-workgroup partial gradients (fixed order => deterministic; pinn_reduce_kernel further down); optionally the
+// optimizer update of the block's parameters right behind it (single-rank steps: no all-reduce in between, two launches less).
 // ------------------------------------------------------------------------------------------------------------
 // bias corrections in double like torch's Python-side scalars (1 - beta ** step); the host computes them when it knows
 // the step (two double pow per thread in the tail of every block otherwise)
@@ -109,9 +108,6 @@ PINN_DEVICE void pinn_optim_update(const PinnOptK& o, float* params, float gi, f
     pinn_optim_apply(o, params, m, v, i, gi, m[i], v[i], params[i], step_size, bc2_sqrt, first);
 }
 
-#ifndef PINN_REDUCE_PB
-#define PINN_REDUCE_PB 32
-#endif
 // ------------------------------------------------------------------------------------------------------------
 // Collocation sampler on the device: replaces the host-side draws of reference model_torch.py:430-434 (`torch.rand`
 // per input column, or `sampler.sample(batch_size)` of a batchflow NumpySampler product `a & b & ...`).
@@ -199,32 +195,61 @@ PINN_AUX_GLOBAL void PINN_LAUNCH_BOUNDS(128) pinn_fit_ctrl_kernel(PinnFitCtrl* d
     if (t < PINN_FIT_CHUNK_MAX) { dst->step_size[t] = a.c.step_size[t]; dst->bc2_sqrt[t] = a.c.bc2_sqrt[t]; }
 }
 
-PINN_AUX_GLOBAL void PINN_LAUNCH_BOUNDS(1024)
-pinn_reduce_kernel(const float* partials, int n_wg, int p_core, float* grads, int accumulate, int do_adam, float* params,
-                   float* m, float* v, const unsigned char* mask, int step_value, float step_size, float bc2_sqrt, PinnOptK opt,
-                   int* step_ptr, float* loss_out, int off_loss, const PinnFitCtrl* ctrl, int ctrl_k, PinnNextBatch next) {
+// ------------------------------------------------------------------------------------------------------------
+// The reduction launch. A block is CH = 32 chunks of workgroup rows x LC lanes per chunk; a lane owns VW consecutive parameters of its
+// chunk's rows and loads them as ONE piece per row: VW = 4, a 16-byte piece (pinn_reduce_kernel, the form the launcher takes whenever the
+// rows allow it), or VW = 1, one dword (pinn_reduce_scalar_kernel: the form this kernel had through round 7, kept for rows that are not
+// 16-byte aligned). The block covers PB = LC * VW parameters. For every parameter the order of the sum is the same in both forms, and
+// in pinn_fit_kernel's sweep (d): chunk c adds rows c, c + CH, c + 2 CH, ... in ascending order in double, the CH chunk sums are added in
+// ascending c in double, the old gradient (accumulate) last, ONE rounding to float. Only which lane loads which element differs.
+// Round 8: the scalar form took 32 parameters per block with 1024 threads -- on BASELINE config 2 (256 rows x 12 756 floats, 13 MB) 399
+// blocks, 6 400 waves of eight 256-byte load instructions each: bound by wave launch and load issue, not by bandwidth. The vector form
+// reads the same bytes with a quarter of the load instructions, 1 KB each, from a quarter of the waves (profiles/r08_reduce_ab.txt).
+// ------------------------------------------------------------------------------------------------------------
+#ifndef PINN_REDUCE_LC
+#define PINN_REDUCE_LC 16       // lanes per chunk of the vector form: 64 parameters per block of 512 threads (the shape sweep of round 8)
+#endif
+#define PINN_REDUCE_CH 32       // chunks of workgroup rows: part of the RESULT (the order of the sums), not a tuning knob
+#define PINN_REDUCE_SCALAR_LC 32
+
+struct PinnReduceArgs {
+    const float* partials; int n_wg, p_core; float* grads; int accumulate, do_adam;
+    float* params; float* m; float* v; const unsigned char* mask;
+    int step_value; float step_size, bc2_sqrt; PinnOptK opt; int* step_ptr; float* loss_out; int off_loss;
+    const PinnFitCtrl* ctrl; int ctrl_k; PinnNextBatch next;
+};
+
+template <int LC, int VW>
+PINN_DEVICE void pinn_reduce_body(const PinnReduceArgs& A) {
     PINN_SMEM(red);
+    constexpr int CH = PINN_REDUCE_CH, PB = LC * VW, NT = LC * CH;      // PB parameters x CH chunks of workgroups per block of NT threads
+    static_assert(VW == 1 || VW == 4, "one dword or one 16-byte piece per lane and row");
+    static_assert(PB <= NT && NT <= 1024, "block shape");
     const int tid = PINN_TID;
-    if (ctrl) {             // (graph replay: this iteration's Adam step and loss slot come from the control block)
-        step_value = ctrl->step0 + ctrl_k;
-        step_size = ctrl->step_size[ctrl_k];
-        bc2_sqrt = ctrl->bc2_sqrt[ctrl_k];
-        loss_out = ctrl->loss_base + ctrl_k;
+    const int n_wg = A.n_wg, p_core = A.p_core;
+    int step_value = A.step_value;
+    float step_size = A.step_size, bc2_sqrt = A.bc2_sqrt;
+    float* loss_out = A.loss_out;
+    if (A.ctrl) {           // (graph replay: this iteration's Adam step and loss slot come from the control block)
+        step_value = A.ctrl->step0 + A.ctrl_k;
+        step_size = A.ctrl->step_size[A.ctrl_k];
+        bc2_sqrt = A.ctrl->bc2_sqrt[A.ctrl_k];
+        loss_out = A.ctrl->loss_base + A.ctrl_k;
     }
-    constexpr int PB = PINN_REDUCE_PB, CH = 1024 / PB;        // PB parameters x CH chunks of workgroups per block
-    const int pl = tid % PB, ch = tid / PB;
-    const int p = PINN_BID * PB + pl;
-    // the operands of the final lanes' Adam update do not depend on the sums: fetched up front, so that their round trip runs under the
+    const int pl = tid % LC, ch = tid / LC;
+    const int p0 = PINN_BID * PB + pl * VW;     // the first of this lane's VW parameters (VW = 4: p_core % 4 == 0, so all four or none)
+    const int p = PINN_BID * PB + tid;          // the final lanes (the first PB threads) own ONE parameter each
+    // the operands of the final lanes' update do not depend on the sums: fetched up front, so that their round trip runs under the
     // row loads instead of behind the barrier (round 5: this kernel took 8 us on BASELINE config 2 -- 4 % of the step -- for 13 MB;
     // it was a chain of dependent round trips: row after row, then the mask, then m / v / the parameter)
     const bool fin = tid < PB && p < p_core;
     bool upd = false;
     float g_old = 0.0f, m_old = 0.0f, v_old = 0.0f, p_old = 0.0f;
     if (fin) {
-        if (accumulate) g_old = grads[p];
-        if (do_adam) {
-            upd = !mask || mask[p];
-            if (upd) { m_old = m[p]; v_old = v[p]; p_old = params[p]; }
+        if (A.accumulate) g_old = A.grads[p];
+        if (A.do_adam) {
+            upd = !A.mask || A.mask[p];
+            if (upd) { m_old = A.m[p]; v_old = A.v[p]; p_old = A.params[p]; }
         }
     }
     // the rows of this thread's chunk, eight loads in flight at a time, summed in ascending row order (as before) -- in DOUBLE since
@@ -232,42 +257,63 @@ pinn_reduce_kernel(const float* partials, int n_wg, int p_core, float* grads, in
     // result) walks through prefix sums far larger than its total, and every fp32 add of this loop rounded at THEIR magnitude: 5e-6
     // relative on that entry from the 256 rows alone (tools/cfg4_bl_probe.py). One rounding to fp32 at the end instead; the adds are
     // free beside the row loads.
-    double s = 0.0;
-    if (p < p_core) {
+    double s[VW];
+#pragma unroll
+    for (int e = 0; e < VW; ++e) s[e] = 0.0;
+    if (p0 < p_core) {
         for (int w0 = ch; w0 < n_wg; w0 += 8 * CH) {
-            float r[8];
+            float r[8][VW];
 #pragma unroll
             for (int j = 0; j < 8; ++j) {
                 const int w = w0 + j * CH;
-                r[j] = (w < n_wg) ? partials[(size_t)w * p_core + p] : 0.0f;
+                const float* src = A.partials + (size_t)w * p_core + p0;
+                if constexpr (VW == 4) {
+                    const f32x4 q = (w < n_wg) ? *reinterpret_cast<const f32x4*>(src) : f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+                    r[j][0] = q[0]; r[j][1] = q[1]; r[j][2] = q[2]; r[j][3] = q[3];
+                } else {
+                    r[j][0] = (w < n_wg) ? src[0] : 0.0f;
+                }
             }
 #pragma unroll
             for (int j = 0; j < 8; ++j)
-                if (w0 + j * CH < n_wg) s += (double)r[j];
+                if (w0 + j * CH < n_wg) {
+#pragma unroll
+                    for (int e = 0; e < VW; ++e) s[e] += (double)r[j][e];
+                }
         }
     }
-    double* red64 = reinterpret_cast<double*>(red);
-    red64[ch * PB + pl] = s;
+    double* red64 = reinterpret_cast<double*>(red);         // [CH][PB]: a lane's VW sums are one 8 VW-byte piece of its chunk's row
+#pragma unroll
+    for (int e = 0; e < VW; ++e) red64[ch * PB + pl * VW + e] = s[e];
     PINN_SYNC();
     if (fin) {
         double t64 = 0.0;
         for (int c = 0; c < CH; ++c) t64 += red64[c * PB + tid];
-        if (accumulate) t64 += (double)g_old;
+        if (A.accumulate) t64 += (double)g_old;
         const float t = (float)t64;
-        grads[p] = t;
-        if (loss_out && p == off_loss) loss_out[0] = t;
-        if (upd) pinn_optim_apply(opt, params, m, v, p, t, m_old, v_old, p_old, step_size, bc2_sqrt, step_value == 1);
+        A.grads[p] = t;
+        if (loss_out && p == A.off_loss) loss_out[0] = t;
+        if (upd) pinn_optim_apply(A.opt, A.params, A.m, A.v, p, t, m_old, v_old, p_old, step_size, bc2_sqrt, step_value == 1);
     }
-    if (do_adam && PINN_BID == 0 && tid == 0) step_ptr[0] = step_value;
+    if (A.do_adam && PINN_BID == 0 && tid == 0) A.step_ptr[0] = step_value;
     // fit chunks: this iteration's tile kernel is through with the batch buffer -- the batch of the next iteration is drawn here
-    // (same generator, same counters as pinn_sample_kernel: bit-identical batches), which saves the iteration a dependent launch
-    if (next.n > 0) {
-        unsigned long long call = next.call;
-        unsigned nk0 = next.k0, nk1 = next.k1;
-        if (ctrl) { call = ctrl->call_index0 + (unsigned long long)(ctrl_k + 1); nk0 = ctrl->k0; nk1 = ctrl->k1; }
-        for (long long i = (long long)PINN_BID * 1024 + tid; i < next.n; i += (long long)PINN_NBLK * 1024)
-            pinn_sample_point(next.xs, i, next.spec, nk0, nk1, (unsigned)(call & 0xffffffffull), (unsigned)(call >> 32));
+    // (same generator, same counters as pinn_sample_kernel: bit-identical batches), which saves the iteration a dependent launch.
+    // A point's words depend on its index alone, so the loop may stride by whatever shape this launch has.
+    if (A.next.n > 0) {
+        unsigned long long call = A.next.call;
+        unsigned nk0 = A.next.k0, nk1 = A.next.k1;
+        if (A.ctrl) { call = A.ctrl->call_index0 + (unsigned long long)(A.ctrl_k + 1); nk0 = A.ctrl->k0; nk1 = A.ctrl->k1; }
+        for (long long i = (long long)PINN_BID * NT + tid; i < A.next.n; i += (long long)PINN_NBLK * NT)
+            pinn_sample_point(A.next.xs, i, A.next.spec, nk0, nk1, (unsigned)(call & 0xffffffffull), (unsigned)(call >> 32));
     }
+}
+
+PINN_AUX_GLOBAL void PINN_LAUNCH_BOUNDS(PINN_REDUCE_LC * PINN_REDUCE_CH) pinn_reduce_kernel(PinnReduceArgs A) {
+    pinn_reduce_body<PINN_REDUCE_LC, 4>(A);
+}
+
+PINN_AUX_GLOBAL void PINN_LAUNCH_BOUNDS(PINN_REDUCE_SCALAR_LC * PINN_REDUCE_CH) pinn_reduce_scalar_kernel(PinnReduceArgs A) {
+    pinn_reduce_body<PINN_REDUCE_SCALAR_LC, 1>(A);
 }
 
 // ------------------------------------------------------------------------------------------------------------

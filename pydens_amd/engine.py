@@ -167,6 +167,10 @@ def bind(lib):
     lib.pinn_last_wgrad_ms.restype = f32
     lib.pinn_last_kernel_name.restype = ctypes.c_char_p
     lib.pinn_last_wgrad_kernel_name.restype = ctypes.c_char_p
+    if hasattr(lib, 'pinn_reduce_rows'):                         # (an experiment build of an earlier source tree may lack them)
+        lib.pinn_reduce_rows.argtypes = [vp, i32, i32, vp, i32, vp, vp, vp, vp, vp, i32, op, vp, i32, vp]
+        lib.pinn_reduce_rows.restype = i32
+        lib.pinn_last_reduce_kernel_name.restype = ctypes.c_char_p
     if hasattr(lib, 'pinn_debug_phase_buffer'):                  # -DPINN_DEBUG_ABI experiment builds only
         lib.pinn_debug_phase_buffer.argtypes = [vp]
     lib.pinn_debug_wgx_chunk_bytes.argtypes = [vp, ctypes.c_longlong]
@@ -189,6 +193,7 @@ ABI_SYMBOLS = ('pinn_create', 'pinn_create_ex', 'pinn_destroy', 'pinn_layout', '
                'pinn_last_tile_ms', 'pinn_last_wgrad_ms', 'pinn_last_kernel_name', 'pinn_last_wgrad_kernel_name', 'pinn_debug_last_kernel',
                'pinn_debug_prepass_in_kernel', 'pinn_debug_wgx_chunk_bytes', 'pinn_debug_max_wgs_per_cu', 'pinn_debug_fit_persistent', 'pinn_fit_chunk_status', 'pinn_set_act_params', 'pinn_debug_fit_onecu_rounds', 'pinn_debug_fit_graph_stats', 'pinn_last_launch_info',
                'pinn_optim_step', 'pinn_optim_step_at', 'pinn_residual_optim_step', 'pinn_fit_steps_optim', 'pinn_fit_steps_optim_graph',
+               'pinn_reduce_rows', 'pinn_last_reduce_kernel_name',
                'pinn_last_error', 'pinn_backend')
 
 _LIB = None
