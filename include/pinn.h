@@ -464,6 +464,27 @@ int pinn_debug_fit_onecu_rounds(pinn_t* net, int rounds);
 /*   pinn_debug_fit_graph_stats    out[0] chunks replayed as launch graphs so far, out[1] graphs captured, out[2] captures the runtime
  *                                 refused (those chunks ran eagerly), out[3] the HIP error code of the last refusal */
 int pinn_debug_fit_graph_stats(int32_t out[4]);
+/*   pinn_port_probe               ONE execution primitive of pydens_amd/csrc/pinn_port.h on the caller's buffers, compiled from the product
+ *                                 sources: the contract test holds the device build and the test build's emulator to one independent statement
+ *                                 of each primitive, bit for bit (tests/test_port_contract.py). n_blocks (1 .. 1024) workgroups of 256 threads
+ *                                 (four waves); g = block * 256 + thread. `which`, and the 4-byte words per BLOCK of `in` / `out`:
+ *                                   0 pinn_mfma16          256 x 8 (a0 b0 a1 b1 c[4]) / 256 x 4: mfma16(a1, b1, mfma16(a0, b0, c))
+ *                                   1 pinn_mfma16_bf16     256 x 12 (a: 4 registers, b: 4, c[4]) / 256 x 4
+ *                                   2 pinn_lds_tr16        4096 (LDS image) + 256 (byte offset per lane, 8-byte aligned, < 16384) / 256 x 2
+ *                                   3 pinn_pack_hi16       256 x 2 (a b) / 256
+ *                                   4 pinn_row_sum16       256 / 256            5 pinn_row_sum16_n<3>  256 x 3 / 256 x 3
+ *                                   6 pinn_row_sum16_f64   256 x 2 (double) / 256 x 2
+ *                                   7 pinn_rows_sum        256 / 256            8 pinn_shfl_xor        256 / 256 x 6 (masks 1, 2, 4, 8, 16, 32)
+ *                                   9 pinn_rows_total_f64  256 x 2 (double) / 256 x 2
+ *                                  10 pinn_wave_uniform    256 / 256
+ *                                  11 pinn_rows, _st4, _ld4  256 x 12 (three f32x4 rows per lane) / 2 x 3072: per wave a slab of 3 rows x 64
+ *                                                          lanes x 16 bytes declared with exactly its size; for the WHOLE call all slabs
+ *                                                          first, then what was read back as [g][row][4]
+ *                                  12 PINN_WAVE_SYNC       256 / 256 x 4 (rounds)
+ *                                  13 pinn_flag_publish / _load / _arrive   256 / 256 x 5; every poll is bounded, a lost flag writes -1
+ *                                  14 pinn_exp2            256 / 256           15 pinn_rcp             256 / 256
+ *                                 Returns non-zero (pinn_last_error) for an unknown `which`, a null buffer or n_blocks out of range. */
+int pinn_port_probe(int which, const void* in, void* out, int n_blocks, void* stream);
 #ifdef PINN_DEBUG_ABI
 /* EXPERIMENT BUILDS ONLY (-DPINN_DEBUG_ABI, tools/variant.sh): the product library neither exports these nor compiles the
  * kernel paths behind them. The flag bits are TIMING experiments -- kernels skip loads / stores / barriers, the results of

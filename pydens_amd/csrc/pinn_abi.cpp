@@ -3,6 +3,7 @@
 #include "pinn_inst.h"
 #include "pinn_fit_kernel.h"
 #include "pinn_aux_kernels.h"
+#include "pinn_port_probe.h"
 
 #include <cstdarg>
 #include <cstdio>
@@ -1466,6 +1467,46 @@ int pinn_reduce_rows(const float* partials, int32_t n_rows, int32_t row_len, flo
     if (step < 1) return fail("step must be >= 1");
     AdamArgs adam = {params, exp_avg, exp_avg_sq, mask, step_ptr, step, k, loss_out, loss_out ? off_loss : -1};
     return launch_reduce(partials, n_rows, row_len, grads, accumulate ? 1 : 0, stream, &adam);
+}
+
+// one primitive of pinn_port.h per call, on the caller's buffers (pinn_port_probe.h: the layouts; tests/test_port_contract.py)
+int pinn_port_probe(int which, const void* in, void* out, int n_blocks, void* stream) {
+    if (which < 0 || which >= PINN_PROBE_COUNT) return fail("unknown port probe %d (0 .. %d)", which, PINN_PROBE_COUNT - 1);
+    if (!in || !out) return fail("null argument");
+    if (n_blocks < 1 || n_blocks > 1024) return fail("n_blocks=%d outside [1, 1024]", n_blocks);
+    const size_t smem = which == PINN_PROBE_LDS_TR16 ? (size_t)PINN_PROBE_LDS_WORDS * 4
+                        : (which == PINN_PROBE_WAVE_SYNC || which == PINN_PROBE_FLAGS) ? 4096 : 0;
+#ifdef PINN_EMU
+    (void)stream;
+#define PINN_PROBE_LAUNCH(kernel, TI, TO) \
+    emu::launch(n_blocks, PINN_PROBE_THREADS, smem, [&] { kernel(static_cast<const TI*>(in), static_cast<TO*>(out)); })
+#else
+#define PINN_PROBE_LAUNCH(kernel, TI, TO) \
+    hipLaunchKernelGGL(kernel, dim3(n_blocks), dim3(PINN_PROBE_THREADS), smem, (hipStream_t)stream, static_cast<const TI*>(in), static_cast<TO*>(out))
+#endif
+    switch (which) {
+        case PINN_PROBE_MFMA16:         PINN_PROBE_LAUNCH(pinn_probe_mfma16, float, float); break;
+        case PINN_PROBE_MFMA16_BF16:    PINN_PROBE_LAUNCH(pinn_probe_mfma16_bf16, unsigned, float); break;
+        case PINN_PROBE_LDS_TR16:       PINN_PROBE_LAUNCH(pinn_probe_lds_tr16, unsigned, unsigned); break;
+        case PINN_PROBE_PACK_HI16:      PINN_PROBE_LAUNCH(pinn_probe_pack_hi16, unsigned, unsigned); break;
+        case PINN_PROBE_ROW_SUM16:      PINN_PROBE_LAUNCH(pinn_probe_row_sum16, float, float); break;
+        case PINN_PROBE_ROW_SUM16_N3:   PINN_PROBE_LAUNCH(pinn_probe_row_sum16_n3, float, float); break;
+        case PINN_PROBE_ROW_SUM16_F64:  PINN_PROBE_LAUNCH(pinn_probe_row_sum16_f64, double, double); break;
+        case PINN_PROBE_ROWS_SUM:       PINN_PROBE_LAUNCH(pinn_probe_rows_sum, float, float); break;
+        case PINN_PROBE_SHFL_XOR:       PINN_PROBE_LAUNCH(pinn_probe_shfl_xor, float, float); break;
+        case PINN_PROBE_ROWS_TOTAL_F64: PINN_PROBE_LAUNCH(pinn_probe_rows_total_f64, double, double); break;
+        case PINN_PROBE_WAVE_UNIFORM:   PINN_PROBE_LAUNCH(pinn_probe_wave_uniform, int, int); break;
+        case PINN_PROBE_ROWS:           PINN_PROBE_LAUNCH(pinn_probe_rows, float, float); break;
+        case PINN_PROBE_WAVE_SYNC:      PINN_PROBE_LAUNCH(pinn_probe_wave_sync, unsigned, unsigned); break;
+        case PINN_PROBE_FLAGS:          PINN_PROBE_LAUNCH(pinn_probe_flags, int, int); break;
+        case PINN_PROBE_EXP2:           PINN_PROBE_LAUNCH(pinn_probe_exp2, float, float); break;
+        default:                        PINN_PROBE_LAUNCH(pinn_probe_rcp, float, float); break;
+    }
+#undef PINN_PROBE_LAUNCH
+#ifndef PINN_EMU
+    if (hipGetLastError() != hipSuccess) return fail("port probe %d: kernel launch failed", which);
+#endif
+    return 0;
 }
 
 }  // extern "C"

@@ -182,6 +182,8 @@ def bind(lib):
     lib.pinn_debug_fit_onecu_rounds.argtypes = [vp, ctypes.c_int]       # (a required symbol like the others: ABI_SYMBOLS)
     lib.pinn_last_launch_info.argtypes = [ctypes.POINTER(ctypes.c_int32)]
     lib.pinn_debug_fit_graph_stats.argtypes = [ctypes.POINTER(ctypes.c_int32)]
+    lib.pinn_port_probe.argtypes = [i32, vp, vp, i32, vp]               # (which, in, out, n_blocks, stream): pinn_port_probe.h
+    lib.pinn_port_probe.restype = i32
     for name in ('pinn_create', 'pinn_create_ex', 'pinn_destroy', 'pinn_layout', 'pinn_jet_forward', 'pinn_jet_forward_ws', 'pinn_jet_backward',
                  'pinn_residual_step', 'pinn_residual_adam_step', 'pinn_adam_step', 'pinn_adam_step_at'):
         getattr(lib, name).restype = i32
@@ -193,7 +195,7 @@ ABI_SYMBOLS = ('pinn_create', 'pinn_create_ex', 'pinn_destroy', 'pinn_layout', '
                'pinn_last_tile_ms', 'pinn_last_wgrad_ms', 'pinn_last_kernel_name', 'pinn_last_wgrad_kernel_name', 'pinn_debug_last_kernel',
                'pinn_debug_prepass_in_kernel', 'pinn_debug_wgx_chunk_bytes', 'pinn_debug_max_wgs_per_cu', 'pinn_debug_fit_persistent', 'pinn_fit_chunk_status', 'pinn_set_act_params', 'pinn_debug_fit_onecu_rounds', 'pinn_debug_fit_graph_stats', 'pinn_last_launch_info',
                'pinn_optim_step', 'pinn_optim_step_at', 'pinn_residual_optim_step', 'pinn_fit_steps_optim', 'pinn_fit_steps_optim_graph',
-               'pinn_reduce_rows', 'pinn_last_reduce_kernel_name',
+               'pinn_reduce_rows', 'pinn_last_reduce_kernel_name', 'pinn_port_probe',
                'pinn_last_error', 'pinn_backend')
 
 _LIB = None

@@ -23,6 +23,7 @@ struct Wave {
     float a[64], b[64];
     unsigned short a16[64][8], b16[64][8];
     unsigned short t16[64][4];
+    int u[64];
     int arrived = 0;
     unsigned gen = 0;
 };
@@ -36,6 +37,7 @@ int g_barrier_count = 0;
 unsigned g_barrier_gen = 0;
 float* g_smem = nullptr;
 unsigned long long g_shuffle = 0, g_rng = 0;
+bool g_strict = true;
 
 unsigned next_random() {                 // xorshift64*
     g_rng ^= g_rng >> 12; g_rng ^= g_rng << 25; g_rng ^= g_rng >> 27;
@@ -134,6 +136,42 @@ float shfl_xor(float v, int mask) {
     return r;
 }
 
+float readlane(float v, int src) {
+    Wave& w = g_waves[g_cur >> 6];
+    w.a[g_cur & 63] = v;
+    wave_sync(w);
+    float r = w.a[src & 63];
+    wave_sync(w);
+    return r;
+}
+
+int wave_uniform(int v) {
+    if (!g_strict) return v;
+    Wave& w = g_waves[g_cur >> 6];
+    const int l = g_cur & 63;
+    w.u[l] = v;
+    wave_sync(w);
+    if (l == 0) {
+        for (int i = 1; i < 64; ++i) {
+            if (w.u[i] == w.u[0]) continue;
+            fprintf(stderr, "emu: pinn_wave_uniform: the lanes of wave %d (block %d) disagree: lane 0 holds %d, lane %d holds %d; all 64:", g_cur >> 6,
+                    g_bid, w.u[0], i, w.u[i]);
+            for (int k = 0; k < 64; ++k) fprintf(stderr, " %d", w.u[k]);
+            fprintf(stderr, "\n");
+            abort();
+        }
+    }
+    const int r = w.u[0];
+    wave_sync(w);
+    return r;
+}
+
+void rows_out_of_bounds(const char* what, int lane_bytes, int row_bytes, unsigned bytes) {
+    fprintf(stderr, "emu: %s beyond the buffer's byte bound: lane_bytes %d + row_bytes %d + 16 > %u (thread %d, block %d)\n", what, lane_bytes,
+            row_bytes, bytes, g_cur, g_bid);
+    abort();
+}
+
 float row_sum16(float v) {
     // same butterfly as the DPP sequence in pinn_port.h: xor 1, xor 2, half-mirror (i <-> 7-i), mirror (i <-> 15-i)
     Wave& w = g_waves[g_cur >> 6];
@@ -154,6 +192,8 @@ void launch(int grid, int block, size_t smem_bytes, const std::function<void()>&
     const char* sh = getenv("PINN_EMU_SHUFFLE");
     g_shuffle = sh ? strtoull(sh, nullptr, 10) : 0;
     if (g_shuffle && !g_rng) g_rng = g_shuffle * 0x9E3779B97F4A7C15ull + 1;
+    const char* st = getenv("PINN_EMU_STRICT");
+    g_strict = !(st && st[0] == '0');
     g_body = &body; g_block = block; g_grid = grid;
     g_fibers.assign(block, Fiber());
     for (auto& f : g_fibers) f.stack = (char*)malloc(kStack);

@@ -26,6 +26,9 @@ float shfl_xor(float v, int mask);
 f32x4 mfma16_bf16(const unsigned short* a8, const unsigned short* b8, f32x4 c);
 void lds_tr16(const void* p, unsigned short* out4);
 float row_sum16(float v);
+float readlane(float v, int src);
+int wave_uniform(int v);
+void rows_out_of_bounds(const char* what, int lane_bytes, int row_bytes, unsigned bytes);
 void launch(int grid, int block, size_t smem_bytes, const std::function<void()>& body);
 }
 
@@ -70,11 +73,27 @@ static inline void pinn_flag_arrive(int* p, bool leader) {
     if (leader) *reinterpret_cast<volatile int*>(p) += 1;
     emu::sync_wave();
 }
-struct PinnRows { char* p; };
-static inline PinnRows pinn_rows(const void* base, unsigned) { return PinnRows{(char*)const_cast<void*>(base)}; }
-static inline f32x4 pinn_rows_ld4(const PinnRows& b, int lane_bytes, int row_bytes) { return *reinterpret_cast<const f32x4*>(b.p + lane_bytes + row_bytes); }
-static inline void pinn_rows_st4(const PinnRows& b, int lane_bytes, int row_bytes, f32x4 v) { *reinterpret_cast<f32x4*>(b.p + lane_bytes + row_bytes) = v; }
-static inline int pinn_wave_uniform(int v) { return v; }
+// the device's buffer resource carries a byte bound: an access beyond it reads zeros or is dropped, silently. Here such an access
+// aborts and names its offsets -- a kernel that runs off the end of its slab must not pass this tier because the memory behind happens
+// to be mapped. (No product kernel relies on the clamp: the split-bf16 fragment loads of pinn_kernel.h stay inside wsp_bytes.)
+struct PinnRows { char* p; unsigned bytes; };
+static inline PinnRows pinn_rows(const void* base, unsigned bytes) { return PinnRows{(char*)const_cast<void*>(base), bytes}; }
+static inline bool pinn_emu_rows_inside(const PinnRows& b, int lane_bytes, int row_bytes) {
+    const long long o = (long long)lane_bytes + (long long)row_bytes;
+    return lane_bytes >= 0 && row_bytes >= 0 && o + 16 <= (long long)b.bytes;
+}
+static inline f32x4 pinn_rows_ld4(const PinnRows& b, int lane_bytes, int row_bytes) {
+    if (!pinn_emu_rows_inside(b, lane_bytes, row_bytes)) emu::rows_out_of_bounds("pinn_rows_ld4", lane_bytes, row_bytes, b.bytes);
+    return *reinterpret_cast<const f32x4*>(b.p + lane_bytes + row_bytes);
+}
+static inline void pinn_rows_st4(const PinnRows& b, int lane_bytes, int row_bytes, f32x4 v) {
+    if (!pinn_emu_rows_inside(b, lane_bytes, row_bytes)) emu::rows_out_of_bounds("pinn_rows_st4", lane_bytes, row_bytes, b.bytes);
+    *reinterpret_cast<f32x4*>(b.p + lane_bytes + row_bytes) = v;
+}
+// the device takes the FIRST active lane's value (v_readfirstlane), whatever the others hold: a value that is not in fact uniform would
+// go unnoticed on both tiers. The emulator checks that the lanes of the wave agree and aborts with the values when they do not
+// (a rendezvous per call; PINN_EMU_STRICT=0, read at launch, switches the check off: every lane then keeps its own value)
+static inline int pinn_wave_uniform(int v) { return emu::wave_uniform(v); }
 static inline float pinn_shfl_xor(float v, int mask) { return emu::shfl_xor(v, mask); }
 static inline float pinn_rows_sum(float x) {
     x += emu::shfl_xor(x, 16);
@@ -93,7 +112,22 @@ static inline double pinn_emu_shfl_xor_f64(double v, int mask) {
     double r; memcpy(&r, &b, 8); return r;
 }
 static inline double pinn_row_sum16_f64(double v) { for (int m = 1; m < 16; m <<= 1) v += pinn_emu_shfl_xor_f64(v, m); return v; }
-static inline double pinn_rows_total_f64(double v) { v += pinn_emu_shfl_xor_f64(v, 16); v += pinn_emu_shfl_xor_f64(v, 32); return v; }
+// the DEVICE's order: the four row values (lanes 0, 16, 32, 48: v_readlane) added in sequence from zero, ((r0 + r1) + r2) + r3 -- not a
+// butterfly, which associates (r0 + r1) + (r2 + r3)
+static inline double pinn_rows_total_f64(double v) {
+    unsigned long long b; memcpy(&b, &v, 8);
+    unsigned lo = (unsigned)(b & 0xffffffffull), hi = (unsigned)(b >> 32);
+    float flo, fhi; memcpy(&flo, &lo, 4); memcpy(&fhi, &hi, 4);
+    double t = 0.0;
+    for (int row = 0; row < 4; ++row) {
+        const float rl = emu::readlane(flo, 16 * row), rh = emu::readlane(fhi, 16 * row);
+        unsigned l, h; memcpy(&l, &rl, 4); memcpy(&h, &rh, 4);
+        const unsigned long long rb = ((unsigned long long)h << 32) | l;
+        double r; memcpy(&r, &rb, 8);
+        t += r;
+    }
+    return t;
+}
 template <int N> static inline void pinn_row_sum16_n(float (&v)[N]) {
     for (int i = 0; i < N; ++i) v[i] = emu::row_sum16(v[i]);
 }
