@@ -499,6 +499,38 @@ int pinn_debug_set_flags(int flags);
 int pinn_debug_phase_buffer(void* buf);
 #endif
 
+/* L-BFGS (torch.optim.LBFGS semantics) on the flat parameter buffer: ONE call computes the next search direction from a freshly
+ * evaluated gradient -- three launches whatever the history size (pydens_amd/csrc/pinn_lbfgs_kernels.h: products with the history in
+ * one pass, the two-loop recursion on m x m scalars in fp64, one combination pass) -- and, with apply_step != 0, takes the fixed step
+ * params += t d in the last of them. The caller owns every buffer and evaluates loss and gradient (the closure); the scalar logic of
+ * a line search stays with the caller too.
+ *   grads        [n] the gradient just evaluated; grads[off_loss] is the loss of that evaluation
+ *   prev_grad, d [n] state: the gradient and the direction of the previous call (zero-filled before the first)
+ *   s_ring, y_ring  [history][ld] state: the stored pairs s = t d, y = g - g_prev by physical slot; ld % 4 == 0, ld >= n. They need no
+ *                initialisation: a slot is written before it is read, entries that take no part are never multiplied in
+ *   mask         [n] or null: entries with mask == 0 enter no product and are never written, in any buffer
+ *   mode         0: `grads` is the first evaluation of an optimizer step (only tolerance_grad can end it), 1: an evaluation inside the
+ *                step's loop (lack of progress -- max |t d| <= tolerance_change, |loss - previous loss| < tolerance_change -- ends it too)
+ *   t            the step length that led from the previous gradient to this one (what the caller read from the control block, or its
+ *                line search's result); lr, tolerance_grad, tolerance_change: torch's
+ *   ctrl         state, the size the ctrl_bytes query returns, ZEROED for a fresh optimizer; doubles:
+ *                [0] live pairs  [1] oldest slot  [2] directions so far (torch's n_iter)  [3] H_diag  [4] t of the new direction
+ *                [5] g . d  [6] max |g|  [7] max |t d|  [8] loss  [9] loss at the previous direction  [10] ys  [11] yy of the last pair
+ *                [12] stop: 0 go on; 1 tolerance_grad, 2 / 3 tolerance_change on the step / the loss -- the state is as before the call;
+ *                     4 g . d > -tolerance_change -- pair, direction and t are stored, no step is taken
+ *                [13] the pair passed torch's curvature test ys > 1e-10 (else ring, matrices and H_diag stay)  [14] its slot
+ *                [15] c_g, then a[history], b[history]: d = c_g g + sum a_j s_j + sum b_j y_j; then s.y and y.y, [history][history]
+ *   workspace    rows of partial sums, the size the workspace_bytes query returns
+ * All buffers 16-byte aligned. history_size up to PINN_LBFGS_MAX_HISTORY (the queries return 0 above it). Bit-repeatable: no atomics,
+ * fixed summation orders. Nothing synchronises; the caller reads ctrl[0 .. 15] back when it needs the decision. */
+#define PINN_LBFGS_MAX_HISTORY 128
+size_t pinn_lbfgs_ctrl_bytes(int32_t history);
+size_t pinn_lbfgs_workspace_bytes(int64_t n, int32_t history);
+int pinn_lbfgs_direction(float* params, const float* grads, float* prev_grad, float* d, float* s_ring, float* y_ring, const uint8_t* mask,
+                         int64_t n, int64_t ld, int32_t history, int32_t mode, int32_t apply_step, int32_t off_loss, float t, double lr,
+                         double tolerance_grad, double tolerance_change, void* ctrl, size_t ctrl_bytes, void* workspace,
+                         size_t workspace_bytes, void* stream);
+
 /* Collocation points drawn on the device: replaces the host-side sampling of model_torch.py:430-434 (d independent
  * `torch.rand((N,1))` columns, or `sampler.sample(N)` of a NumpySampler product `a & b & ...`, README.md:82) with ONE
  * launch that fills xs [n_points][d] row-major.  Column c is kind[c]: PINN_SAMPLE_UNIFORM a[c] + (b[c] - a[c]) * u,

@@ -4,7 +4,9 @@
 #include "pinn_fit_kernel.h"
 #include "pinn_aux_kernels.h"
 #include "pinn_port_probe.h"
+#include "pinn_lbfgs_kernels.h"
 
+#include <atomic>
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
@@ -1467,6 +1469,69 @@ int pinn_reduce_rows(const float* partials, int32_t n_rows, int32_t row_len, flo
     if (step < 1) return fail("step must be >= 1");
     AdamArgs adam = {params, exp_avg, exp_avg_sq, mask, step_ptr, step, k, loss_out, loss_out ? off_loss : -1};
     return launch_reduce(partials, n_rows, row_len, grads, accumulate ? 1 : 0, stream, &adam);
+}
+
+// ---- L-BFGS direction (pinn_lbfgs_kernels.h): three launches per inner iteration, whatever the history size --------------------------
+static size_t lbfgs_ctrl_doubles(int m) { return (size_t)PINN_LBFGS_CTRL_HEAD + 2 * (size_t)m + 2 * (size_t)m * m; }
+
+size_t pinn_lbfgs_ctrl_bytes(int32_t history) {
+    if (history < 1 || history > PINN_LBFGS_MAX_HISTORY) return 0;
+    return lbfgs_ctrl_doubles(history) * sizeof(double);
+}
+
+size_t pinn_lbfgs_workspace_bytes(int64_t n, int32_t history) {
+    if (n < 1 || history < 1 || history > PINN_LBFGS_MAX_HISTORY) return 0;
+    const size_t rows = (size_t)((n + PINN_LBFGS_DOTS_SLICE - 1) / PINN_LBFGS_DOTS_SLICE);
+    return rows * (5 * (size_t)history + PINN_LBFGS_ROW_TAIL) * sizeof(double);
+}
+
+int pinn_lbfgs_direction(float* params, const float* grads, float* prev_grad, float* d, float* s_ring, float* y_ring, const uint8_t* mask,
+                         int64_t n, int64_t ld, int32_t history, int32_t mode, int32_t apply_step, int32_t off_loss, float t, double lr,
+                         double tolerance_grad, double tolerance_change, void* ctrl, size_t ctrl_bytes, void* workspace,
+                         size_t workspace_bytes, void* stream) {
+    if (!params || !grads || !prev_grad || !d || !s_ring || !y_ring || !ctrl || !workspace) return fail("null argument");
+    if (history < 1 || history > PINN_LBFGS_MAX_HISTORY)
+        return fail("L-BFGS history_size=%d outside [1, %d]", history, PINN_LBFGS_MAX_HISTORY);
+    if (n < 1 || n > (int64_t)1 << 40) return fail("L-BFGS: n=%lld entries", (long long)n);
+    if (ld < n || ld % 4 != 0) return fail("L-BFGS: row stride %lld of the rings must be a multiple of 4 and at least n=%lld", (long long)ld, (long long)n);
+    if (off_loss < 0 || off_loss >= n) return fail("off_loss=%d outside the gradient buffer", off_loss);
+    if (mode != 0 && mode != 1) return fail("L-BFGS: mode=%d (0: first evaluation of a step, 1: inside its loop)", mode);
+    if (!(lr >= 0.0)) return fail("L-BFGS: invalid learning rate %g", lr);
+    const void* aligned[] = {params, grads, prev_grad, d, s_ring, y_ring, ctrl, workspace};
+    for (const void* p : aligned)
+        if (reinterpret_cast<uintptr_t>(p) & 15) return fail("L-BFGS: buffers must be 16-byte aligned");
+    if (ctrl_bytes < pinn_lbfgs_ctrl_bytes(history)) return fail("L-BFGS: control block too small (%zu < %zu bytes)", ctrl_bytes, pinn_lbfgs_ctrl_bytes(history));
+    if (workspace_bytes < pinn_lbfgs_workspace_bytes(n, history))
+        return fail("workspace too small (%zu < %zu bytes)", workspace_bytes, pinn_lbfgs_workspace_bytes(n, history));
+    const int m = history, rowlen = 5 * m + PINN_LBFGS_ROW_TAIL;
+    const int blocks = (int)((n + PINN_LBFGS_SLICE - 1) / PINN_LBFGS_SLICE);                   // the combine pass
+    const int rows = (int)((n + PINN_LBFGS_DOTS_SLICE - 1) / PINN_LBFGS_DOTS_SLICE);           // the dots pass: one row of partial sums each
+    PinnLbfgsArgs A = {params, grads, prev_grad, d, s_ring, y_ring, mask, (long long)n, (long long)ld, m, mode, apply_step ? 1 : 0, off_loss, t,
+                       lr, tolerance_grad, tolerance_change, static_cast<double*>(ctrl), static_cast<double*>(workspace), rows};
+    const size_t smem_dots = 4 * (size_t)rowlen * sizeof(double);
+    const size_t smem_fin = ((size_t)rowlen + 7 * (size_t)m + (size_t)m * m) * sizeof(double);
+#ifdef PINN_EMU
+    (void)stream;
+    emu::launch(rows, PINN_LBFGS_THREADS, smem_dots, [&] { pinn_lbfgs_dots_kernel(A); });
+    emu::launch(1, PINN_LBFGS_THREADS, smem_fin, [&] { pinn_lbfgs_finalize_kernel(A); });
+    emu::launch(blocks, PINN_LBFGS_THREADS, 0, [&] { pinn_lbfgs_combine_kernel(A); });
+#else
+    // (the finalize pass stages the s.y matrix in LDS: above 64 KB from history_size 85; the attribute is raised once per device and size)
+    static std::atomic<size_t> fin_attr[64];                  // (host threads may race to their first call: the worst case is the attribute set twice)
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return fail("L-BFGS: no current device");
+    if (smem_fin > 48 * 1024 && smem_fin > fin_attr[dev].load(std::memory_order_relaxed)) {
+        if (hipFuncSetAttribute(reinterpret_cast<const void*>(pinn_lbfgs_finalize_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                (int)smem_fin) != hipSuccess)
+            return fail("L-BFGS: %zu bytes of LDS for history_size=%d refused", smem_fin, m);
+        fin_attr[dev].store(smem_fin, std::memory_order_relaxed);
+    }
+    hipLaunchKernelGGL(pinn_lbfgs_dots_kernel, dim3(rows), dim3(PINN_LBFGS_THREADS), smem_dots, (hipStream_t)stream, A);
+    hipLaunchKernelGGL(pinn_lbfgs_finalize_kernel, dim3(1), dim3(PINN_LBFGS_THREADS), smem_fin, (hipStream_t)stream, A);
+    hipLaunchKernelGGL(pinn_lbfgs_combine_kernel, dim3(blocks), dim3(PINN_LBFGS_THREADS), 0, (hipStream_t)stream, A);
+    if (hipGetLastError() != hipSuccess) return fail("L-BFGS kernel launch failed");
+#endif
+    return 0;
 }
 
 // one primitive of pinn_port.h per call, on the caller's buffers (pinn_port_probe.h: the layouts; tests/test_port_contract.py)

@@ -20,6 +20,10 @@ SAMPLE_UNIFORM, SAMPLE_NORMAL, SAMPLE_CONST = 0, 1, 2
 RES_PROGRAM, RES_AFFINE = 0, 1
 CRIT_MSE, CRIT_L1, CRIT_SMOOTH_L1, CRIT_HUBER = 0, 1, 2, 3      # include/pinn.h PINN_CRIT_*
 OPT_ADAM, OPT_ADAMW, OPT_SGD, OPT_RMSPROP = 0, 1, 2, 3             # include/pinn.h PINN_OPT_*
+LBFGS_MAX_HISTORY = 128                                            # include/pinn.h PINN_LBFGS_MAX_HISTORY
+# the first doubles of pinn_lbfgs_direction's control block
+LBFGS_CTRL = ('count', 'head', 'n_iter', 'H_diag', 't', 'gtd', 'gmax', 'smax', 'loss', 'prev_loss', 'ys', 'yy', 'stop', 'pushed', 'slot', 'c_g')
+LBFGS_START, LBFGS_LOOP = 0, 1                                     # `mode` of pinn_lbfgs_direction
 SKIP_PRE = 0x100         # include/pinn.h PINN_SKIP_PRE
 ACT_CODES = {'tanh': 0, 'sigmoid': 1, 'sin': 2, 'identity': 3, 'softplus': 4, 'silu': 5, 'swish': 5, 'gelu': 6,
              # round 5 (include/pinn.h PINN_ACT_RELU ..): torch-default forms
@@ -184,6 +188,14 @@ def bind(lib):
     lib.pinn_debug_fit_graph_stats.argtypes = [ctypes.POINTER(ctypes.c_int32)]
     lib.pinn_port_probe.argtypes = [i32, vp, vp, i32, vp]               # (which, in, out, n_blocks, stream): pinn_port_probe.h
     lib.pinn_port_probe.restype = i32
+    f64 = ctypes.c_double
+    lib.pinn_lbfgs_ctrl_bytes.argtypes = [i32]
+    lib.pinn_lbfgs_ctrl_bytes.restype = ctypes.c_size_t
+    lib.pinn_lbfgs_workspace_bytes.argtypes = [i64, i32]
+    lib.pinn_lbfgs_workspace_bytes.restype = ctypes.c_size_t
+    lib.pinn_lbfgs_direction.argtypes = [vp, vp, vp, vp, vp, vp, vp, i64, i64, i32, i32, i32, i32, f32, f64, f64, f64, vp, ctypes.c_size_t,
+                                         vp, ctypes.c_size_t, vp]
+    lib.pinn_lbfgs_direction.restype = i32
     for name in ('pinn_create', 'pinn_create_ex', 'pinn_destroy', 'pinn_layout', 'pinn_jet_forward', 'pinn_jet_forward_ws', 'pinn_jet_backward',
                  'pinn_residual_step', 'pinn_residual_adam_step', 'pinn_adam_step', 'pinn_adam_step_at'):
         getattr(lib, name).restype = i32
@@ -196,6 +208,7 @@ ABI_SYMBOLS = ('pinn_create', 'pinn_create_ex', 'pinn_destroy', 'pinn_layout', '
                'pinn_debug_prepass_in_kernel', 'pinn_debug_wgx_chunk_bytes', 'pinn_debug_max_wgs_per_cu', 'pinn_debug_fit_persistent', 'pinn_fit_chunk_status', 'pinn_set_act_params', 'pinn_debug_fit_onecu_rounds', 'pinn_debug_fit_graph_stats', 'pinn_last_launch_info',
                'pinn_optim_step', 'pinn_optim_step_at', 'pinn_residual_optim_step', 'pinn_fit_steps_optim', 'pinn_fit_steps_optim_graph',
                'pinn_reduce_rows', 'pinn_last_reduce_kernel_name', 'pinn_port_probe',
+               'pinn_lbfgs_ctrl_bytes', 'pinn_lbfgs_workspace_bytes', 'pinn_lbfgs_direction',
                'pinn_last_error', 'pinn_backend')
 
 _LIB = None
@@ -541,3 +554,28 @@ class Net:
             else:
                 self._raise(self.lib.pinn_optim_step(_ptr(params), _ptr(grads), _ptr(exp_avg), _ptr(exp_avg_sq), _ptr(mask),
                                                      params.numel(), _ptr(step), ctypes.byref(optim), _stream(params)))
+
+    # ---- L-BFGS (include/pinn.h pinn_lbfgs_direction) --------------------------------------------------------------------------------
+    def lbfgs_ctrl_doubles(self, history):
+        return int(self.lib.pinn_lbfgs_ctrl_bytes(int(history))) // 8
+
+    def lbfgs_workspace_bytes(self, n, history):
+        return int(self.lib.pinn_lbfgs_workspace_bytes(int(n), int(history)))
+
+    def lbfgs_direction(self, params, grads, prev_grad, d, s_ring, y_ring, mask, history, mode, apply_step, t, lr, tolerance_grad,
+                        tolerance_change, ctrl, workspace, off_loss=None, stream=None):
+        """ the next L-BFGS direction from the gradient in `grads` (three launches; with `apply_step` the fixed step params += t d rides in
+        the last); the decision and the scalars are in ctrl[:16] afterwards (LBFGS_CTRL) -- nothing is read back here """
+        for t_, name in ((params, 'params'), (grads, 'grads'), (prev_grad, 'prev_grad'), (d, 'd'), (s_ring, 's_ring'), (y_ring, 'y_ring')):
+            _check(t_, name)
+        _check(mask, 'mask', torch.uint8)
+        _check(ctrl, 'ctrl', torch.float64)
+        n = params.numel()
+        if s_ring.dim() != 2 or s_ring.shape != y_ring.shape or s_ring.shape[0] != history:
+            raise ValueError(f's_ring and y_ring must be [{history}, ld]')
+        with _on_device(params):
+            self._raise(self.lib.pinn_lbfgs_direction(
+                _ptr(params), _ptr(grads), _ptr(prev_grad), _ptr(d), _ptr(s_ring), _ptr(y_ring), _ptr(mask), n, s_ring.shape[1], int(history),
+                int(mode), int(bool(apply_step)), int(self.layout.off_loss if off_loss is None else off_loss), float(t), float(lr),
+                float(tolerance_grad), float(tolerance_change), _ptr(ctrl), ctrl.numel() * 8, _ptr(workspace),
+                workspace.numel() * workspace.element_size(), _stream(params) if stream is None else stream))

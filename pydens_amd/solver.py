@@ -36,6 +36,7 @@ class FlatOptimizer:
     (include/pinn.h pinn_optim_t): Adam and AdamW with weight decay, SGD, RMSprop -- two state arrays at most, the model's two moment
     buffers. `exp_avg` / `exp_avg_sq` name those buffers for every rule; the torch names of what a rule keeps in them are aliases. """
     # rule -> (code, the keywords it takes besides lr)
+    needs_closure = False       # (FlatLBFGS, and TorchOptimizerAdapter around torch.optim.LBFGS: stepped as `step(closure)`)
     RULES = {'Adam': (engine.OPT_ADAM, ('betas', 'eps', 'weight_decay')),
              'AdamW': (engine.OPT_ADAMW, ('betas', 'eps', 'weight_decay')),
              'SGD': (engine.OPT_SGD, ('momentum', 'dampening', 'nesterov', 'weight_decay')),
@@ -170,6 +171,151 @@ class FlatAdam(FlatOptimizer):
                                  self.lr, self.betas, self.eps, at=self.t, loss_out=loss_out, stream=stream)
 
 
+class FlatLBFGS(FlatOptimizer):
+    """ torch.optim.LBFGS(lr, max_iter, max_eval, tolerance_grad, tolerance_change, history_size, line_search_fn in (None, 'strong_wolfe')) on
+    the flat kernel buffer (include/pinn.h pinn_lbfgs_direction). `step(grads, closure=...)` is torch's `step(closure)`: the same stopping
+    rules in the same order, `func_evals` and `n_iter` counted the same way. Per closure evaluation the direction costs three launches --
+    whatever the history size -- and ONE read-back of sixteen doubles; without a line search the last launch also takes the step. The
+    strong-Wolfe search is torch's own `torch.optim.lbfgs._strong_wolfe` over the flat buffers.
+    State on the device, owned by the model like the Adam moments: the rings `S`, `Y` [history_size][p_total] (rows padded to 16 bytes),
+    `prev_grad`, `d`, and the control block `ctrl` (ring head and count, H_diag, t, gtd, max|g|, max|t d|, losses, ys / yy of the last pair,
+    the combination coefficients and the two Gram matrices). `fit(optimizer=None)` carries all of it on. """
+    KEYWORDS = ('max_iter', 'max_eval', 'tolerance_grad', 'tolerance_change', 'history_size', 'line_search_fn')
+    # the rings may take this many bytes (2 * history_size * p_total * 4); above it the fit keeps torch.optim.LBFGS, which allocates its
+    # history pair by pair as the iterations accept them. 1 GiB: torch's default history of 100 up to 1.3 million parameters.
+    HISTORY_BUDGET = 1 << 30
+    needs_closure = True
+
+    @classmethod
+    def hyper(cls, name, lr, kwargs):
+        """ torch's resolved hyper-parameters if the kernels carry `torch.optim.LBFGS(params, lr=lr, **kwargs)`, else None: another keyword, a
+        tensor-valued hyper-parameter, an unknown line search. torch's own argument checks raise here as they do there. """
+        if name != 'LBFGS' or set(kwargs) - set(cls.KEYWORDS):
+            return None
+        number = lambda v: isinstance(v, (int, float)) and not isinstance(v, bool)
+        integer = lambda v: isinstance(v, int) and not isinstance(v, bool)
+        if not number(lr) or not all(number(kwargs.get(key, 0.0)) for key in ('tolerance_grad', 'tolerance_change')):
+            return None
+        if not integer(kwargs.get('max_iter', 20)) or not integer(kwargs.get('history_size', 100)) or kwargs.get('history_size', 100) < 1:
+            return None
+        if not (kwargs.get('max_eval') is None or integer(kwargs['max_eval'])) or kwargs.get('line_search_fn') not in (None, 'strong_wolfe'):
+            return None
+        return dict(torch.optim.LBFGS([torch.zeros(1, requires_grad=True)], lr=lr, **kwargs).defaults)
+
+    @classmethod
+    def refusal(cls, model, hyper):
+        """ why the kernels do not take this history, in words (None: they do) """
+        history, p_total = hyper['history_size'], model.flat.numel()
+        need = 2 * history * p_total * 4
+        if need > cls.HISTORY_BUDGET:
+            return (f'L-BFGS history on the device: 2 * history_size * p_total * 4 = 2 * {history} * {p_total} * 4 = {need} bytes exceed the '
+                    f'budget of {cls.HISTORY_BUDGET} bytes (FlatLBFGS.HISTORY_BUDGET); this fit keeps torch.optim.LBFGS')
+        if history > engine.LBFGS_MAX_HISTORY:
+            return (f'L-BFGS history_size={history}: the kernels run the recursion on history_size x history_size scalars in the LDS of one '
+                    f'workgroup, which holds {engine.LBFGS_MAX_HISTORY}; this fit keeps torch.optim.LBFGS')
+        return None
+
+    def __init__(self, model, lr=1, **kwargs):
+        hyper = self.hyper('LBFGS', lr, kwargs)
+        if hyper is None:
+            raise NotImplementedError(f'the HIP optimizer kernels do not carry torch.optim.LBFGS(lr={lr}, **{kwargs})')
+        message = self.refusal(model, hyper)
+        if message is not None:
+            raise NotImplementedError(message)
+        self.name, self.hyper_parameters, self.optim = 'LBFGS', hyper, None
+        self.torch_kwargs = dict(kwargs)
+        self.model, self.lr = model, hyper['lr']
+        history, flat = hyper['history_size'], model.flat
+        ld = (flat.numel() + 3) // 4 * 4
+        net = model.net
+        state = getattr(model, '_lbfgs_state', None)
+        if state is None or state['S'].shape != (history, ld) or state['S'].device != flat.device:
+            # (the model's, at the same addresses from fit to fit, like the Adam moments)
+            state = model._lbfgs_state = dict(
+                S=torch.zeros((history, ld), dtype=torch.float32, device=flat.device), Y=torch.zeros((history, ld), dtype=torch.float32, device=flat.device),
+                prev_grad=torch.zeros_like(flat), d=torch.zeros_like(flat),
+                ctrl=torch.zeros(net.lbfgs_ctrl_doubles(history), dtype=torch.float64, device=flat.device),
+                rows=torch.zeros(net.lbfgs_workspace_bytes(flat.numel(), history) // 8, dtype=torch.float64, device=flat.device))
+        else:
+            for buf in state.values():
+                buf.zero_()
+        self.S, self.Y, self.prev_grad, self.d, self.ctrl, self.rows = (state[key] for key in ('S', 'Y', 'prev_grad', 'd', 'ctrl', 'rows'))
+        self.func_evals, self.n_iter, self.step_length = 0, 0, 0.0      # torch's state['func_evals'], ['n_iter'], ['t']
+        self.closure_calls = 0                                          # ... of the last step
+        self.last = None                                                # the control block's head as last read
+        self.t, self.mask, self.members, self.calls = 0, None, None, []         # (FlatOptimizer.refresh: fit calls served, members, mask)
+
+    def lagging(self, offsets):
+        return []               # (one state for the whole buffer in torch too: nothing per parameter to fall behind)
+
+    @property
+    def state(self):
+        """ torch's state dict entries that are scalars, read from the device """
+        head = dict(zip(engine.LBFGS_CTRL, self.ctrl[:len(engine.LBFGS_CTRL)].tolist()))
+        return dict(func_evals=self.func_evals, n_iter=self.n_iter, t=self.step_length, H_diag=head['H_diag'], history=int(head['count']),
+                    prev_loss=head['prev_loss'])
+
+    def _direction(self, grads, mode, apply, stream):
+        hp = self.hyper_parameters
+        self.model.net.lbfgs_direction(self.model.flat, grads, self.prev_grad, self.d, self.S, self.Y, self.mask, hp['history_size'], mode,
+                                       apply, self.step_length, hp['lr'], hp['tolerance_grad'], hp['tolerance_change'], self.ctrl, self.rows,
+                                       stream=stream)
+        self.last = dict(zip(engine.LBFGS_CTRL, self.ctrl[:len(engine.LBFGS_CTRL)].tolist()))       # the ONE read-back per evaluation
+        return self.last
+
+    def step(self, grads, loss_out=None, stream=None, closure=None):
+        """ torch.optim.LBFGS.step(closure); `closure()` fills `grads` (loss slot included). Returns the first evaluation's loss (0-d, on the
+        device). """
+        if closure is None:
+            raise TypeError("FlatLBFGS.step() needs the closure that re-evaluates loss and gradient")
+        from torch.optim.lbfgs import _strong_wolfe
+        hp, flat = self.hyper_parameters, self.model.flat
+        off_loss = self.model.net.layout.off_loss
+        max_iter, max_eval, search = hp['max_iter'], hp['max_eval'], hp['line_search_fn']
+        self.closure_calls = 0
+
+        def evaluate():
+            closure()
+            self.closure_calls += 1
+        evaluate()
+        first = grads[off_loss].clone()
+        self.func_evals += 1
+        evals, n_iter, mode, g = 1, 0, engine.LBFGS_START, grads
+        live = None
+        while n_iter < max_iter:
+            c = self._direction(g, mode, search is None, stream)
+            if c['stop'] in (1.0, 2.0, 3.0):            # optimality in front of the first direction; inside the loop also lack of progress
+                break
+            n_iter += 1
+            self.n_iter += 1
+            self.step_length = c['t']
+            if c['stop'] == 4.0:                        # directional derivative above -tolerance_change: no step
+                break
+            ls_evals = 0
+            if search is not None:
+                x0, d = flat.clone(), self.d
+                live = self.mask.bool() if live is None else live
+
+                def objective(x, t, d):
+                    # (masked entries keep their bits: d is zero there, but -0.0 + 0.0 is not -0.0)
+                    flat.copy_(torch.where(live, torch.add(x, d, alpha=float(t)), x))
+                    evaluate()
+                    return float(grads[off_loss]), grads.clone()
+                loss, g, t, ls_evals = _strong_wolfe(objective, x0, c['t'], d, c['loss'], g, c['gtd'], max_ls=max_eval - evals)
+                flat.copy_(torch.where(live, torch.add(x0, d, alpha=float(t)), x0))
+                self.step_length = float(t)
+            elif n_iter != max_iter:                    # (the step was taken by the direction's last launch)
+                evaluate()
+                ls_evals, g = 1, grads
+            evals += ls_evals
+            self.func_evals += ls_evals
+            if n_iter == max_iter or evals >= max_eval:
+                break
+            mode = engine.LBFGS_LOOP
+        self.t += 1
+        return first
+
+
 class TorchOptimizerAdapter:
     """ any other `torch.optim` optimizer the reference accepts by name (model_torch.py:420): torch updates the
     parameter views in place; their .grad are views of the flat gradient buffer the kernels fill. """
@@ -209,7 +355,39 @@ class TorchOptimizerAdapter:
     def refresh(self):
         pass
 
-    def step(self, grads, loss_out=None, stream=None):
+    @property
+    def needs_closure(self):
+        """ torch.optim.LBFGS: `step(closure)` re-evaluates loss and gradient on the same batch, as often as its rule asks """
+        import inspect
+        closure = inspect.signature(type(self.opt).step).parameters.get('closure')
+        return closure is not None and closure.default is inspect.Parameter.empty
+
+    def step(self, grads, loss_out=None, stream=None, closure=None):
+        """ closure: the gradient part of the iteration on the batch already drawn; it fills `grads` (loss slot included). With one, the
+        optimizer is stepped as `loss = opt.step(closure)` and that loss -- the first evaluation's -- is returned.
+        Under torch.distributed the closure ends in the all-reduce, so every rank sees the same gradient and loss and holds the same
+        parameters: every rank takes the same decisions (line search, stopping rules) and makes the same number of closure calls -- the
+        collectives inside them pair up without any further agreement between the ranks. """
+        if closure is not None:
+            off_loss = self.model.net.layout.off_loss
+            self.closure_calls = 0
+
+            def evaluate():
+                closure()
+                self.closure_calls += 1
+                self._bind(grads, contiguous=True)      # (torch.optim.LBFGS flattens every .grad with view(-1))
+                return grads[off_loss].clone()          # (a copy: the slot is overwritten by the next evaluation)
+            try:
+                return self.opt.step(evaluate)
+            finally:
+                for p in self.params:
+                    p.grad = None
+        self._bind(grads)
+        self.opt.step()
+        for p in self.params:
+            p.grad = None
+
+    def _bind(self, grads, contiguous=False):
         # Parameters WITHOUT a gradient are skipped by torch's optimizers -- no weight decay, no momentum step, no step count -- and the
         # reference's backward leaves `.grad = None` on (a) a parameter frozen since this optimizer was built (`fit(optimizer=None)` after
         # freeze_trainable) and (b) a scalar the loss of this call does not reach: `log_scale` without an initial condition, a V(...) of the
@@ -223,9 +401,8 @@ class TorchOptimizerAdapter:
         for p in self.params:
             reached = p.requires_grad and id(p) not in zero
             p.grad = grads.as_strided(tuple(p.shape), tuple(p.stride()), p.storage_offset()) if reached else None
-        self.opt.step()
-        for p in self.params:
-            p.grad = None
+            if contiguous and reached:
+                p.grad = p.grad.contiguous()
 
 
 class Solver:
@@ -250,6 +427,7 @@ class Solver:
         self.optimizer = None
         self.optimizer_path = 'torch'       # set_optimizer_path: optimizers other than plain Adam as torch.optim code or on the fused kernels
         self.last_fit_optimizer = None
+        self.optimizer_refusal = None       # why the last `fit(optimizer='LBFGS')` under the 'fused' path kept torch.optim (None: it did not)
         if os.environ.get('PYDENS_AMD_OPTIMIZER'):
             self.set_optimizer_path(os.environ['PYDENS_AMD_OPTIMIZER'])
 
@@ -322,11 +500,30 @@ class Solver:
         launches behind the gradient reduction) or 'fused' -- Adam and AdamW with weight decay, SGD (momentum, dampening, nesterov, weight
         decay) and RMSprop (alpha, weight decay, momentum OR centered) are applied by the kernels (include/pinn.h pinn_optim_t): in the
         gradient reduction's launch, in the fit chunks and their launch graphs, in the one-CU chunk kernel. Matched by exact name and
-        keywords; anything else (amsgrad, maximize, ..., other optimizers) stays on torch.optim in either setting.
+        keywords; anything else (amsgrad, maximize, ..., other optimizers) stays on torch.optim in either setting. L-BFGS (lr, max_iter,
+        max_eval, tolerance_grad, tolerance_change, history_size, line_search_fn None or 'strong_wolfe') becomes `FlatLBFGS`: direction
+        kernels at three launches per closure evaluation; under data parallelism, with other keywords or with a history beyond
+        `FlatLBFGS.HISTORY_BUDGET` bytes it stays torch.optim.LBFGS, which `fit` steps through a closure on either path.
         `last_fit_optimizer` tells, e.g. 'AdamW/fused'. Process-wide: PYDENS_AMD_OPTIMIZER. """
         if path not in self.OPTIMIZER_PATHS:
             raise ValueError(f'optimizer path {path!r}: expected one of {sorted(self.OPTIMIZER_PATHS)}')
         self.optimizer_path = path
+
+    def _lbfgs_on_the_kernels(self, optimizer, lr, kwargs):
+        """ does `fit(optimizer='LBFGS', ...)` take FlatLBFGS under the 'fused' optimizer path? Not with other keywords or tensor-valued
+        hyper-parameters, not under data parallelism (every rank would keep a history of the same all-reduced gradients: torch.optim does that),
+        not with a history beyond the memory budget -- `optimizer_refusal` then says why, with the byte count. """
+        self.optimizer_refusal = None
+        if optimizer != 'LBFGS':
+            return False
+        hyper = FlatLBFGS.hyper(optimizer, lr, kwargs)
+        if hyper is None or self._world()[1] > 1:
+            return False
+        self.optimizer_refusal = FlatLBFGS.refusal(self.model, hyper)
+        if self.optimizer_refusal is not None:
+            import warnings
+            warnings.warn('pydens_amd: ' + self.optimizer_refusal, RuntimeWarning)
+        return self.optimizer_refusal is None
 
     def _lower_criterion(self, criterion):
         """ (code, parameter, sum) of a criterion the point stage has in closed form, else None. By EXACT type: a subclass may override
@@ -986,6 +1183,8 @@ class Solver:
                 self.optimizer = FlatAdam(model, lr=lr, **kwargs)
             elif self.optimizer_path == 'fused' and FlatOptimizer.hyper(optimizer, lr, kwargs) is not None:
                 self.optimizer = FlatOptimizer(model, optimizer, lr=lr, **kwargs)
+            elif self.optimizer_path == 'fused' and self._lbfgs_on_the_kernels(optimizer, lr, kwargs):
+                self.optimizer = FlatLBFGS(model, lr=lr, **kwargs)
             else:
                 self.optimizer = TorchOptimizerAdapter(model, optimizer, lr, **kwargs)
         elif self.optimizer is None:
@@ -1035,7 +1234,8 @@ class Solver:
         self._apply_criterion(crit if fused else (engine.CRIT_MSE, 0.0, False), nums_constraints)
         flat_adam = isinstance(self.optimizer, FlatOptimizer)       # (any rule of the kernels; FlatAdam is the default one)
         self.last_fit_optimizer = f"{self.optimizer.name}/{'fused' if flat_adam else 'torch'}"
-        one_launch = fused and world == 1 and flat_adam and tuple(loss_terms) == ('equation',)
+        # (an optimizer that steps through a closure -- L-BFGS -- re-evaluates the batch: no fit chunks, launch graphs or one-launch form)
+        one_launch = fused and world == 1 and flat_adam and tuple(loss_terms) == ('equation',) and not self.optimizer.needs_closure
         stream = engine.stream_of(model.flat)           # looked up once per call, not per iteration
         history_ptr = history.data_ptr()
         try:
@@ -1052,8 +1252,23 @@ class Solver:
             # the common case end to end on the device: chunks of iterations enqueued by ONE library call each
             # (pinn_fit_steps: sample, fused step, Adam per iteration; the interpreter is out of the per-iteration path)
             return self._fit_chunks(niters, local_batch, sampler, columns, stream, history, done)
+        by_closure = self.optimizer.needs_closure
         for it in tqdm(range(niters), disable=None):
             xs = self._sample(local_batch, sampler, stream)
+            if by_closure:
+                # the batch is drawn ONCE; every closure call re-runs the gradient part of the iteration on it, and the iteration's loss is
+                # what `step(closure)` returns: the loss at its first evaluation (`loss = opt.step(closure)`)
+                def closure(xs=xs):
+                    if fused:
+                        self._fused_terms_step(xs, loss_terms, nums_constraints, world, stream=stream)
+                    else:
+                        self._generic_step(xs, loss_terms, nums_constraints, criterion, world)      # (eager: no launch graph across closure calls)
+                    if world > 1:
+                        self._all_reduce(stream)
+                loss = self.optimizer.step(self.grads, stream=stream, closure=closure)
+                history[it:it + 1].copy_(loss.reshape(1))
+                done[0] = it + 1
+                continue
             if one_launch:
                 # Adam rides in the gradient-reduction launch, which also drops the loss into history[it]
                 self._fused_step(xs, 1, adam=self.optimizer, loss_out=history_ptr + 4 * it, stream=stream)
