@@ -811,7 +811,7 @@ PINN_DEVICE void pinn_prog_backward(const pinn_program_t& pg, const float* regs,
             case PINN_OP_TANH: adj[a * T] += g * (1.0f - y * y); break;
             case PINN_OP_SQRT: adj[a * T] += g * 0.5f / y; break;
             case PINN_OP_POW: { const float e = pg.consts[b]; adj[a * T] += g * e * powf(x, e - 1.0f); } break;
-            case PINN_OP_ABS: adj[a * T] += (x >= 0.0f ? g : -g); break;
+            case PINN_OP_ABS: adj[a * T] += (x > 0.0f ? g : x < 0.0f ? -g : 0.0f); break;      // sign(0) = 0 (torch's abs backward)
             case PINN_OP_SIGMOID: adj[a * T] += g * y * (1.0f - y); break;
             case PINN_OP_RECIP: adj[a * T] -= g * y * y; break;
             default: adj[a * T] += g; break;
@@ -897,6 +897,10 @@ PINN_DEVICE void pinn_point_prefetch(const PinnKArgs& A, const float* params_, l
     // aux_: the rows of the x-only pre-pass -- A.aux, or the LDS copy of the one-CU fit chunk (pinn_fit_kernel.h)
     constexpr int S = pinn_ns(ND, N2P);
     using SH = PinnShape<SPEC, ND>;
+    // lanes of a ragged (or empty) tile that hold no point: an in-bounds address, and a ZERO in place of what is there -- with the
+    // pre-pass in the kernel prologue every workgroup writes the rows of its OWN points only, so row entry 0 belongs to another
+    // workgroup (a race), and in recycled workspace memory the stale value may be a NaN that a zero upstream gradient does not remove
+    // (the source term alone feeds r, which the point stage masks by `valid`)
     const long long gi = valid ? gidx : 0;
     pre.src = A.src_const;
 #pragma unroll
@@ -907,9 +911,9 @@ PINN_DEVICE void pinn_point_prefetch(const PinnKArgs& A, const float* params_, l
 #pragma unroll
             for (int s = 0; s < S; ++s)
                 if (s < SH::s_user(A))
-                    pre.cs[s] = (SH::coef_row(A, s) >= 0) ? aux_[(long long)SH::coef_row(A, s) * A.n_points + gi] : A.coef[s];
+                    pre.cs[s] = (SH::coef_row(A, s) >= 0) ? (valid ? aux_[(long long)SH::coef_row(A, s) * A.n_points + gi] : 0.0f) : A.coef[s];
         } else {
-            for (int m = 0; m < A.n_aux; ++m) pregs[(S + SH::d(A) + m) * T] = aux_[(long long)m * A.n_points + gi];
+            for (int m = 0; m < A.n_aux; ++m) pregs[(S + SH::d(A) + m) * T] = valid ? aux_[(long long)m * A.n_points + gi] : 0.0f;
         }
     }
     if (SH::has_ic(A)) {
@@ -921,7 +925,7 @@ PINN_DEVICE void pinn_point_prefetch(const PinnKArgs& A, const float* params_, l
             // callable IC lowered into the x-only pre-pass (value + derivative streams as aux rows / constants)
 #pragma unroll
             for (int s = 0; s < S; ++s)
-                if (s < SH::s_user(A)) pre.ic[s] = (A.ic_row[s] >= 0) ? aux_[(long long)A.ic_row[s] * A.n_points + gi] : A.ic_cst[s];
+                if (s < SH::s_user(A)) pre.ic[s] = (A.ic_row[s] >= 0) ? (valid ? aux_[(long long)A.ic_row[s] * A.n_points + gi] : 0.0f) : A.ic_cst[s];
         } else {
             pre.ic[0] = (!SH::FIXED && A.ic_var1 > 0) ? params_[A.off_extra + A.ic_var1 - 1] : A.ic_const;
         }
@@ -1164,9 +1168,11 @@ PINN_DEVICE void pinn_point_stage(const PinnKArgs& A, const float* params_, cons
         float w = valid ? 2.0f * r * A.inv_n : 0.0f;
         out.loss = valid ? r * r * A.inv_n : 0.0f;
         if (SH::crit(A) != PINN_CRIT_MSE && valid) pinn_criterion(SH::crit(A), A.crit_param, r, A.inv_n, out.loss, w);
-        pinn_prog_backward(A.prog, pregs, padj, T, w);          // seeded with d(loss)/dr: adjoints come out scaled
+        // (a lane without a point runs no reverse sweep: its registers hold zeros, where a quotient or a logarithm is not finite, and
+        //  0 * inf would reach the weight gradients and the adjoints of the V(...) registers; its adjoints stay zero)
+        if (valid) pinn_prog_backward(A.prog, pregs, padj, T, w);          // seeded with d(loss)/dr: adjoints come out scaled
 #pragma unroll
-        for (int s = 0; s < S; ++s) { gu[s] = padj[s * T]; padj[s * T] = 0.0f; }
+        for (int s = 0; s < S; ++s) { gu[s] = valid ? padj[s * T] : 0.0f; padj[s * T] = 0.0f; }
         for (int c = 0; c < SH::d(A) + A.n_aux; ++c) padj[(S + c) * T] = 0.0f;
     } else {
         if (valid) {

@@ -391,6 +391,9 @@ class Sym:
             return Sym.make('MUL', self, self)
         if e == 1.0:
             return self
+        if e == 0.0:
+            # torch: x ** 0 = 1 with gradient 0, at x = 0 as well; the interpreter's adjoint e * powf(x, e - 1) would be 0 * inf there
+            return Sym('const', value=1.0)
         return Sym('op', op='POW', args=(self,), value=e)
 
     def __rpow__(self, o):

@@ -117,3 +117,29 @@ def close_or_arbitrated(got, want32, want64_fn, rtol, atol=1e-9, k=2.0, note=Non
         ea, eb = np.delete(ea, ia), np.delete(eb, ib)
     err64, ref64, scale64 = float(np.linalg.norm(ea)), float(np.linalg.norm(eb)), float(np.linalg.norm(c))
     return outliers_ok and err64 <= max(k * ref64, rtol * scale64 + floor), err64 / max(scale64, 1e-30), True
+
+
+# ---- a short Adam trajectory against the oracle (test_fuzz_equations.py, test_residual_program_ops.py) ------------------------------------
+FIT_LOSS_RTOL, FIT_PARAM_RTOL = 2e-5, 2e-5          # SURVEY 8c items 2 - 4 (were 5e-5 / 2e-4)
+
+
+def fit_close(test, case, solver, oracle32, oracle64_fn, param_atol=2e-6, adam_move=None):
+    """ losses and final parameters of a short Adam trajectory against the fp32 oracle at the survey's bar; a case the reference's own
+    fp32 arithmetic cannot hold is arbitrated by the fp64 oracle stepped from the same start:
+    |ours - f64| <= max(2 |ref32 - f64|, bar). Adam turns the fp32 noise of a SMALL gradient entry into a move of size lr, hence the
+    absolute floor per parameter entry. """
+    arb = {}
+
+    def o64():
+        if 'o' not in arb:
+            arb['o'] = oracle64_fn()
+        return arb['o']
+    got_l, want_l = [float(v) for v in solver.losses], [float(v) for v in oracle32.losses]
+    ok, err, a = close_or_arbitrated(got_l, want_l, lambda: [float(v) for v in o64().losses], FIT_LOSS_RTOL, atol=0.0)
+    record_margin(test, case, 'losses', err, FIT_LOSS_RTOL, a)
+    assert ok, (case, got_l, want_l, err)
+    p64 = None
+    for i, (got, ref) in enumerate(zip(export_params(solver), oracle32.export_params())):
+        ok, err, a = close_or_arbitrated(got, ref, lambda i=i: o64().export_params()[i], FIT_PARAM_RTOL, atol=param_atol, adam_move=adam_move)
+        record_margin(test, case, 'parameters', err, FIT_PARAM_RTOL, a)
+        assert ok, (case, i, err)

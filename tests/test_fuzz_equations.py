@@ -11,7 +11,8 @@ import pytest
 import torch
 
 from conftest import params_close, rel_l2
-from helpers import FixedBatches, close_or_arbitrated, export_params, load_params, record_margin
+from helpers import (FIT_LOSS_RTOL, FIT_PARAM_RTOL, FixedBatches, close_or_arbitrated, export_params, fit_close, load_params,
+                     record_margin)
 
 SCALE = int(os.environ.get('PINN_FUZZ_SCALE', '1'))       # soak runs: PINN_FUZZ_SCALE=8 pytest tests/test_fuzz_equations.py -m gpu
 LEAVES = ['u', 'ux', 'ut', 'uxx', 'x', 't', 'c']
@@ -59,29 +60,8 @@ def _ev(tree, env):
     return {'add': a + b, 'sub': a - b, 'mul': a * b}[kind]
 
 
-LOSS_RTOL, PARAM_RTOL = 2e-5, 2e-5          # SURVEY 8c items 2 - 4 (were 5e-5 / 2e-4)
-
-
-def _fit_close(test, case, solver, oracle32, oracle64_fn, param_atol=2e-6, adam_move=None):
-    """ losses and final parameters of a short Adam trajectory against the fp32 oracle at the survey's bar; a case the reference's own
-    fp32 arithmetic cannot hold is arbitrated by the fp64 oracle stepped from the same start:
-    |ours - f64| <= max(2 |ref32 - f64|, bar). Adam turns the fp32 noise of a SMALL gradient entry into a move of size lr, hence the
-    absolute floor per parameter entry. """
-    arb = {}
-
-    def o64():
-        if 'o' not in arb:
-            arb['o'] = oracle64_fn()
-        return arb['o']
-    got_l, want_l = [float(v) for v in solver.losses], [float(v) for v in oracle32.losses]
-    ok, err, a = close_or_arbitrated(got_l, want_l, lambda: [float(v) for v in o64().losses], LOSS_RTOL, atol=0.0)
-    record_margin(test, case, 'losses', err, LOSS_RTOL, a)
-    assert ok, (case, got_l, want_l, err)
-    p64 = None
-    for i, (got, ref) in enumerate(zip(export_params(solver), oracle32.export_params())):
-        ok, err, a = close_or_arbitrated(got, ref, lambda i=i: o64().export_params()[i], PARAM_RTOL, atol=param_atol, adam_move=adam_move)
-        record_margin(test, case, 'parameters', err, PARAM_RTOL, a)
-        assert ok, (case, i, err)
+LOSS_RTOL, PARAM_RTOL = FIT_LOSS_RTOL, FIT_PARAM_RTOL          # (helpers.fit_close: shared with test_residual_program_ops.py)
+_fit_close = fit_close
 
 
 def _uses(tree, name):
