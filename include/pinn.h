@@ -531,6 +531,31 @@ int pinn_lbfgs_direction(float* params, const float* grads, float* prev_grad, fl
                          double tolerance_grad, double tolerance_change, void* ctrl, size_t ctrl_bytes, void* workspace,
                          size_t workspace_bytes, void* stream);
 
+/* Residual-adaptive collocation sampling (RAD: Wu et al., CMAME 2023): n_out rows of `pool` [m][d] (fp32, row-major, d <= 8,
+ * m <= 2^22) drawn with replacement with probability proportional to q_i = w_i + floor_c * mean(w), w_i = |r_i|^power in double
+ * (power 1 or 2; a non-finite r_i has weight 0), mean(w) = sum(w) / m.  Inverse CDF over the inclusive fp64 prefix sums P of q:
+ * output row i takes ONE Philox4x32-10 block with counter (i low, i high, call low, call high), u = ((w0 >> 5) * 2^26 + (w1 >> 6)) * 2^-53,
+ * t = u * P[m-1], and copies the pool row j with the smallest P[j] > t (never a row of zero weight while any weight is positive);
+ * idx_out (optional, int32 [n_out]) receives j.  sum(q) == 0: uniform, j = min(m - 1, floor(u * m)).
+ * Key: every block code of the counter of pinn_sample_points is in use, so this stream differs from that one by its KEY:
+ * z = seed ^ 0x5245534D504C4552; z = (z ^ z >> 30) * 0xBF58476D1CE4E5B9; z = (z ^ z >> 27) * 0x94D049BB133111EB; z ^= z >> 31
+ * (the splitmix64 finaliser), key = (z low, z high); pinn_sample_points keys with (seed low, seed high) itself.
+ * Three launches (weights + block-local scans, scan of the block totals by one workgroup, the draw), fixed summation order, no
+ * atomics, nothing read back: the rows depend on (pool, r, power, floor_c, seed, call) alone, bit for bit.  `workspace`: caller-owned,
+ * 16-byte aligned, pinn_resample_workspace_bytes(m) bytes; it holds the prefix sums afterwards, and pinn_resample_redraw draws again
+ * from it -- same pool and m, fresh (seed, call) -- with the third launch alone.  n_out == 0 succeeds and launches NOTHING: such a
+ * call does not fill the workspace either, and a redraw needs a workspace that a call with n_out >= 1 has filled.
+ * floor_c must lie in [0, PINN_RESAMPLE_MAX_FLOOR]: up to there floor_c * mean(w) and every prefix sum stay finite for any fp32
+ * residuals (w <= 1.2e77, m <= 2^22); beyond it the floor term dwarfs every weight anyway (the draw is uniform) and larger values,
+ * which could overflow the sums, are refused like a negative or non-finite one. */
+#define PINN_RESAMPLE_MAX_FLOOR 1e100
+size_t pinn_resample_workspace_bytes(int64_t m);
+int pinn_resample_points(const float* pool, const float* r, int64_t m, int d, int power, double floor_c, int64_t n_out,
+                         uint64_t seed, uint64_t call_index, float* xs_out, int32_t* idx_out, void* workspace, size_t workspace_bytes,
+                         void* stream);
+int pinn_resample_redraw(const float* pool, int64_t m, int d, int64_t n_out, uint64_t seed, uint64_t call_index, float* xs_out,
+                         int32_t* idx_out, const void* workspace, size_t workspace_bytes, void* stream);
+
 /* Collocation points drawn on the device: replaces the host-side sampling of model_torch.py:430-434 (d independent
  * `torch.rand((N,1))` columns, or `sampler.sample(N)` of a NumpySampler product `a & b & ...`, README.md:82) with ONE
  * launch that fills xs [n_points][d] row-major.  Column c is kind[c]: PINN_SAMPLE_UNIFORM a[c] + (b[c] - a[c]) * u,

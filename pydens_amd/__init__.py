@@ -9,6 +9,6 @@ from .tokens import D, V, current_model
 from .model import TorchModel, ConvBlockModel
 from .solver import Solver
 from .sampler import *            # noqa: F401,F403  (reference re-exports batchflow.sampler.*)
-from .sampler import NumpySampler, NS, Sampler, ConstantSampler
+from .sampler import NumpySampler, NS, Sampler, ConstantSampler, ResidualSampler
 
 __version__ = '0.1.0'

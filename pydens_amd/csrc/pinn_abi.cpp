@@ -1534,6 +1534,71 @@ int pinn_lbfgs_direction(float* params, const float* grads, float* prev_grad, fl
     return 0;
 }
 
+// ---- residual-adaptive resampler (pinn_aux_kernels.h: three launches; the redraw is the third alone) -----------------------------------
+static int resample_nb(int64_t m) { return (int)((m + PINN_RESAMPLE_BLOCK - 1) / PINN_RESAMPLE_BLOCK); }
+
+size_t pinn_resample_workspace_bytes(int64_t m) {
+    if (m < 1 || m > PINN_RESAMPLE_MAX_POOL) return 0;
+    const size_t doubles = (size_t)PINN_RESAMPLE_HEAD + (size_t)m + 2 * (size_t)resample_nb(m);
+    return (doubles * sizeof(double) + 15) / 16 * 16;
+}
+
+static int resample_launch(const float* pool, const float* r, int64_t m, int d, int power, double floor_c, int64_t n_out, uint64_t seed,
+                           uint64_t call_index, float* xs_out, int32_t* idx_out, void* workspace, size_t workspace_bytes, void* stream,
+                           bool fill) {
+    if (!pool || (fill && !r) || (n_out > 0 && !xs_out)) return fail("resample: null argument");
+    if (m < 1 || m > PINN_RESAMPLE_MAX_POOL) return fail("resample: pool of m=%lld points outside [1, %lld]", (long long)m, (long long)PINN_RESAMPLE_MAX_POOL);
+    if (n_out < 0) return fail("resample: n_out=%lld", (long long)n_out);
+    if (d < 1 || d > PINN_MAX_INPUTS) return fail("resample: d=%d outside [1, %d]", d, PINN_MAX_INPUTS);
+    if (fill && power != 1 && power != 2) return fail("resample: power=%d (1 or 2)", power);
+    if (fill && !(floor_c >= 0.0 && floor_c <= PINN_RESAMPLE_MAX_FLOOR))
+        return fail("resample: floor=%g must lie in [0, %g] (finite, not negative; larger values could overflow the prefix sums)", floor_c, PINN_RESAMPLE_MAX_FLOOR);
+    if (!workspace) return fail("resample: null workspace");
+    if (reinterpret_cast<uintptr_t>(workspace) & 15) return fail("resample: the workspace must be 16-byte aligned");
+    if (workspace_bytes < pinn_resample_workspace_bytes(m))
+        return fail("resample: workspace too small (%zu < %zu bytes)", workspace_bytes, pinn_resample_workspace_bytes(m));
+    if (n_out == 0) return 0;                   // (nothing at all: the workspace is not filled either, include/pinn.h)
+    unsigned long long z = seed ^ 0x5245534D504C4552ull;
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    z ^= z >> 31;
+    const int nb = resample_nb(m);
+    double* ws = static_cast<double*>(workspace);
+    PinnResampleArgs A = {pool, r, (long long)m, d, power, floor_c, (long long)n_out, (unsigned)(z & 0xffffffffull), (unsigned)(z >> 32),
+                          (unsigned)(call_index & 0xffffffffull), (unsigned)(call_index >> 32), xs_out, idx_out,
+                          ws, ws + PINN_RESAMPLE_HEAD, ws + PINN_RESAMPLE_HEAD + m, ws + PINN_RESAMPLE_HEAD + m + nb, nb};
+    const int draw_blocks = (int)((n_out + PINN_RESAMPLE_BLOCK - 1) / PINN_RESAMPLE_BLOCK);
+    const size_t smem = (PINN_RESAMPLE_BLOCK / 64) * sizeof(double);
+#ifdef PINN_EMU
+    (void)stream;
+    if (fill) {
+        emu::launch(nb, PINN_RESAMPLE_BLOCK, smem, [&] { pinn_resample_weights_kernel(A); });
+        emu::launch(1, PINN_RESAMPLE_BLOCK, smem, [&] { pinn_resample_offsets_kernel(A); });
+    }
+    if (n_out > 0) emu::launch(draw_blocks, PINN_RESAMPLE_BLOCK, 0, [&] { pinn_resample_draw_kernel(A); });
+#else
+    if (fill) {
+        hipLaunchKernelGGL(pinn_resample_weights_kernel, dim3(nb), dim3(PINN_RESAMPLE_BLOCK), smem, (hipStream_t)stream, A);
+        hipLaunchKernelGGL(pinn_resample_offsets_kernel, dim3(1), dim3(PINN_RESAMPLE_BLOCK), smem, (hipStream_t)stream, A);
+    }
+    if (n_out > 0) hipLaunchKernelGGL(pinn_resample_draw_kernel, dim3(draw_blocks), dim3(PINN_RESAMPLE_BLOCK), 0, (hipStream_t)stream, A);
+    if (hipGetLastError() != hipSuccess) return fail("resample kernel launch failed");
+#endif
+    return 0;
+}
+
+int pinn_resample_points(const float* pool, const float* r, int64_t m, int d, int power, double floor_c, int64_t n_out,
+                         uint64_t seed, uint64_t call_index, float* xs_out, int32_t* idx_out, void* workspace, size_t workspace_bytes,
+                         void* stream) {
+    return resample_launch(pool, r, m, d, power, floor_c, n_out, seed, call_index, xs_out, idx_out, workspace, workspace_bytes, stream, true);
+}
+
+int pinn_resample_redraw(const float* pool, int64_t m, int d, int64_t n_out, uint64_t seed, uint64_t call_index, float* xs_out,
+                         int32_t* idx_out, const void* workspace, size_t workspace_bytes, void* stream) {
+    return resample_launch(pool, nullptr, m, d, 1, 0.0, n_out, seed, call_index, xs_out, idx_out, const_cast<void*>(workspace),
+                           workspace_bytes, stream, false);
+}
+
 // one primitive of pinn_port.h per call, on the caller's buffers (pinn_port_probe.h: the layouts; tests/test_port_contract.py)
 int pinn_port_probe(int which, const void* in, void* out, int n_blocks, void* stream) {
     if (which < 0 || which >= PINN_PROBE_COUNT) return fail("unknown port probe %d (0 .. %d)", which, PINN_PROBE_COUNT - 1);

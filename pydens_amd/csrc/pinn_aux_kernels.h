@@ -401,3 +401,156 @@ pinn_sample_kernel(float* xs, long long n, PinnSampleSpec spec, unsigned k0, uns
     }
     pinn_sample_point(xs, i, spec, k0, k1, call_lo, call_hi);
 }
+
+// ------------------------------------------------------------------------------------------------------------
+// Residual-adaptive resampler (include/pinn.h pinn_resample_points): draws n_out rows of a pool of M candidate points with probability
+// proportional to q_i = w_i + c, w_i = |r_i|^power in double (power 1 or 2: exact from the fp32 residual; a non-finite r_i counts 0),
+// c = floor * mean(w) -- RAD of Wu, Zhu, Tan, Kartha, Lu, "A comprehensive study of non-adaptive and residual-based adaptive sampling for
+// physics-informed neural networks" (CMAME 2023), kept unnormalised. Selection by inverse CDF over fp64 prefix sums, three launches:
+//   1. pinn_resample_weights_kernel: block b of 256 threads owns points 256 b .. 256 b + 255: w, the block-local inclusive scan L_w and
+//      the block total T_w[b] = L_w[last].
+//   2. pinn_resample_offsets_kernel (ONE workgroup): S = sum_b T_w[b], c = floor * (S / M), then the inclusive scan E of the block totals
+//      of q, T_q[b] = T_w[b] + n_b c (n_b points in block b); head = {E[nb - 1], c, S, M}.
+//   3. pinn_resample_draw_kernel: one thread per output row i. One Philox4x32-10 block, counter (i_lo, i_hi, call_lo, call_hi), key = the
+//      folded seed; u = ((w0 >> 5) 2^26 + (w1 >> 6)) 2^-53, t = u E[nb - 1]; b = the smallest block with E[b] > t (binary search), then
+//      inside it the smallest l with E[b - 1] + (L_w[l] + (l + 1) c) > t -- or, where rounding leaves none, the block's last point of
+//      positive q; row 256 b + l of the pool is copied. E[nb - 1] == 0 (no positive weight, floor 0): j = min(M - 1, floor(u M)).
+// A redraw (period > 1) is launch 3 alone on a filled workspace.
+// The order of every sum is fixed by the 256-thread block shape, which is part of the RESULT like PINN_REDUCE_CH: inside a wave the
+// butterfly of pinn_block_scan_f64, the four wave totals in ascending order, the block totals in passes of 256 with a running carry.
+// Two properties of that order carry the selection: the scans never decrease, and a term that is exactly zero leaves its prefix
+// bit-equal to its left neighbour's (at wave, block and pass borders too) -- so "the smallest index whose prefix exceeds t" is never
+// a point of zero weight while any weight is positive, on either level of the search. No atomics, nothing read back.
+// ------------------------------------------------------------------------------------------------------------
+#define PINN_RESAMPLE_BLOCK 256
+#define PINN_RESAMPLE_MAX_POOL (1ll << 22)      // 16 384 block totals: 64 passes of the one workgroup of launch 2
+#define PINN_RESAMPLE_HEAD 4                    // doubles in front of the workspace: E[nb - 1], c, S, M
+
+struct PinnResampleArgs {
+    const float* pool; const float* r; long long m; int d, power; double floor_c;
+    long long n_out; unsigned k0, k1, call_lo, call_hi; float* xs_out; int* idx_out;
+    double* head; double* local; double* tot; double* ends; int nb;      // workspace: head[4] | L_w[m] | T_w[nb] | E[nb]
+};
+
+PINN_DEVICE double pinn_lane_xor_f64(double v, int mask) {
+#ifdef PINN_EMU
+    return pinn_emu_shfl_xor_f64(v, mask);
+#else
+    return __shfl_xor(v, mask, 64);
+#endif
+}
+
+// inclusive scan of one double per thread over the 256 threads of a workgroup; every thread also gets the total. Wave level: a butterfly
+// -- after step k a lane holds the total of its aligned group of 2^(k+1) lanes (lower half + upper half) and, in `pre`, its inclusive
+// prefix inside that group (lanes of the upper half add the lower half's total in front). lds: 4 doubles, free again on return.
+PINN_DEVICE double pinn_block_scan_f64(double v, double* lds, double* total) {
+    const int lane = PINN_TID & 63, wave = PINN_TID >> 6;
+    double pre = v, tot = v;
+    for (int k = 0; k < 6; ++k) {
+        const double t = pinn_lane_xor_f64(tot, 1 << k);
+        if (lane & (1 << k)) { pre = t + pre; tot = t + tot; }
+        else tot = tot + t;
+    }
+    if (lane == 63) lds[wave] = tot;            // (== pre of the wave's last lane)
+    PINN_SYNC();
+    double off = 0.0, all = 0.0;
+    for (int w = 0; w < PINN_RESAMPLE_BLOCK / 64; ++w) {
+        if (w == wave) off = all;
+        all += lds[w];
+    }
+    PINN_SYNC();
+    *total = all;
+    return off + pre;
+}
+
+// prefix of q from the prefix of w: l + 1 points of floor term c each (two roundings, never contracted: the emulator and the device agree)
+PINN_DEVICE double pinn_resample_prefix(double lw, int l, double c) {
+#pragma clang fp contract(off)
+    const double t = (double)(l + 1) * c;
+    return lw + t;
+}
+
+PINN_AUX_GLOBAL void PINN_LAUNCH_BOUNDS(PINN_RESAMPLE_BLOCK) pinn_resample_weights_kernel(PinnResampleArgs A) {
+    PINN_SMEM(sm);
+    double* lds = reinterpret_cast<double*>(sm);
+    const long long i = (long long)PINN_BID * PINN_RESAMPLE_BLOCK + PINN_TID;
+    double w = 0.0;
+    if (i < A.m) {
+        const double a = fabs((double)A.r[i]);
+        if (a <= 3.4028234663852886e38) w = A.power == 2 ? a * a : a;       // (false for inf and NaN: weight 0)
+    }
+    double total;
+    const double p = pinn_block_scan_f64(w, lds, &total);
+    if (i < A.m) A.local[i] = p;
+    if (PINN_TID == 0) A.tot[PINN_BID] = total;
+}
+
+PINN_AUX_GLOBAL void PINN_LAUNCH_BOUNDS(PINN_RESAMPLE_BLOCK) pinn_resample_offsets_kernel(PinnResampleArgs A) {
+    PINN_SMEM(sm);
+    double* lds = reinterpret_cast<double*>(sm);
+    const int tid = PINN_TID, nb = A.nb;
+    double sum_w = 0.0;
+    for (int b0 = 0; b0 < nb; b0 += PINN_RESAMPLE_BLOCK) {
+        double total;
+        pinn_block_scan_f64(b0 + tid < nb ? A.tot[b0 + tid] : 0.0, lds, &total);
+        sum_w += total;
+    }
+    const double c = A.floor_c * (sum_w / (double)A.m);
+    double carry = 0.0;
+    for (int b0 = 0; b0 < nb; b0 += PINN_RESAMPLE_BLOCK) {
+        const int b = b0 + tid;
+        double q = 0.0;
+        if (b < nb) {
+            const long long left = A.m - (long long)b * PINN_RESAMPLE_BLOCK;
+            q = pinn_resample_prefix(A.tot[b], (int)(left < PINN_RESAMPLE_BLOCK ? left : PINN_RESAMPLE_BLOCK) - 1, c);
+        }
+        double total;
+        const double incl = pinn_block_scan_f64(q, lds, &total);
+        if (b < nb) A.ends[b] = carry + incl;
+        carry += total;
+    }
+    if (tid == 0) { A.head[0] = carry; A.head[1] = c; A.head[2] = sum_w; A.head[3] = (double)A.m; }
+}
+
+PINN_AUX_GLOBAL void PINN_LAUNCH_BOUNDS(PINN_RESAMPLE_BLOCK) pinn_resample_draw_kernel(PinnResampleArgs A) {
+    const long long i = (long long)PINN_BID * PINN_RESAMPLE_BLOCK + PINN_TID;
+    if (i >= A.n_out) return;
+    unsigned r[4];
+    pinn_philox4x32_10((unsigned)((unsigned long long)i & 0xffffffffull), (unsigned)((unsigned long long)i >> 32), A.call_lo, A.call_hi,
+                       A.k0, A.k1, r);
+    const double u = (double)(((unsigned long long)(r[0] >> 5) << 26) | (unsigned long long)(r[1] >> 6)) * 1.1102230246251565e-16;   // 2^-53
+    const double total = A.head[0], c = A.head[1];
+    long long j;
+    if (!(total > 0.0)) {
+        j = (long long)(u * (double)A.m);
+        if (j > A.m - 1) j = A.m - 1;
+    } else {
+        const double t = u * total;
+        const int nb = A.nb;
+        const double last_e = A.ends[nb - 1];
+        int lo = 0, hi = nb - 1;                // E[hi] > t or E[hi] is the first block end that reaches the total: the search cannot run off
+        while (lo < hi) {
+            const int mid = (lo + hi) >> 1;
+            const double e = A.ends[mid];
+            if (e > t || e >= last_e) hi = mid; else lo = mid + 1;
+        }
+        const int b = lo;
+        const double off = b > 0 ? A.ends[b - 1] : 0.0;
+        const long long base = (long long)b * PINN_RESAMPLE_BLOCK;
+        const long long left = A.m - base;
+        const int n_b = (int)(left < PINN_RESAMPLE_BLOCK ? left : PINN_RESAMPLE_BLOCK);
+        const double* lw = A.local + base;
+        const double last_q = pinn_resample_prefix(lw[n_b - 1], n_b - 1, c);
+        lo = 0; hi = n_b - 1;
+        while (lo < hi) {
+            const int mid = (lo + hi) >> 1;
+            const double q = pinn_resample_prefix(lw[mid], mid, c);
+            if (off + q > t || q >= last_q) hi = mid; else lo = mid + 1;
+        }
+        j = base + lo;
+    }
+    const float* src = A.pool + j * A.d;
+    float* dst = A.xs_out + i * A.d;
+    for (int k = 0; k < A.d; ++k) dst[k] = src[k];
+    if (A.idx_out) A.idx_out[i] = (int)j;
+}

@@ -196,6 +196,13 @@ def bind(lib):
     lib.pinn_lbfgs_direction.argtypes = [vp, vp, vp, vp, vp, vp, vp, i64, i64, i32, i32, i32, i32, f32, f64, f64, f64, vp, ctypes.c_size_t,
                                          vp, ctypes.c_size_t, vp]
     lib.pinn_lbfgs_direction.restype = i32
+    u64 = ctypes.c_uint64
+    lib.pinn_resample_workspace_bytes.argtypes = [i64]
+    lib.pinn_resample_workspace_bytes.restype = ctypes.c_size_t
+    lib.pinn_resample_points.argtypes = [vp, vp, i64, i32, i32, f64, i64, u64, u64, vp, vp, vp, ctypes.c_size_t, vp]
+    lib.pinn_resample_points.restype = i32
+    lib.pinn_resample_redraw.argtypes = [vp, i64, i32, i64, u64, u64, vp, vp, vp, ctypes.c_size_t, vp]
+    lib.pinn_resample_redraw.restype = i32
     for name in ('pinn_create', 'pinn_create_ex', 'pinn_destroy', 'pinn_layout', 'pinn_jet_forward', 'pinn_jet_forward_ws', 'pinn_jet_backward',
                  'pinn_residual_step', 'pinn_residual_adam_step', 'pinn_adam_step', 'pinn_adam_step_at'):
         getattr(lib, name).restype = i32
@@ -209,6 +216,7 @@ ABI_SYMBOLS = ('pinn_create', 'pinn_create_ex', 'pinn_destroy', 'pinn_layout', '
                'pinn_optim_step', 'pinn_optim_step_at', 'pinn_residual_optim_step', 'pinn_fit_steps_optim', 'pinn_fit_steps_optim_graph',
                'pinn_reduce_rows', 'pinn_last_reduce_kernel_name', 'pinn_port_probe',
                'pinn_lbfgs_ctrl_bytes', 'pinn_lbfgs_workspace_bytes', 'pinn_lbfgs_direction',
+               'pinn_resample_workspace_bytes', 'pinn_resample_points', 'pinn_resample_redraw',
                'pinn_last_error', 'pinn_backend')
 
 _LIB = None
@@ -389,7 +397,10 @@ class Net:
     def workspace_bytes(self, n_points, nd, n2):
         return int(self.lib.pinn_workspace_bytes(self.handle, n_points, nd, n2))
 
-    def jet_forward(self, params, xs, dir_cols=(), n2=0, ic_streams=None, ic_const=0.0, out=None):
+    def jet_forward(self, params, xs, dir_cols=(), n2=0, ic_streams=None, ic_const=0.0, out=None, ws_slot='_fwd_ws'):
+        """ ws_slot: which scratch buffer of this object a nested-skip forward uses. The step's forward keeps `_fwd_ws`, whose address a
+        recorded launch graph of the generic step carries; `Solver.residual` passes a slot of its own, so that a pool larger than any batch
+        never reallocates the buffer under such a graph. """
         _check(params, 'params'); _check(xs, 'xs'); _check(ic_streams, 'ic_streams')
         n = xs.shape[0]
         dirs, nd = self._dirs(dir_cols)
@@ -400,11 +411,12 @@ class Net:
         with _on_device(params):
             if self.nested:
                 need = self.workspace_bytes(n, nd, n2)
-                if self._fwd_ws is None or self._fwd_ws.numel() * 4 < need or self._fwd_ws.device != xs.device:
-                    self._fwd_ws = torch.empty((need + 3) // 4, dtype=torch.float32, device=xs.device)
+                ws = getattr(self, ws_slot, None)
+                if ws is None or ws.numel() * 4 < need or ws.device != xs.device:
+                    ws = torch.empty((need + 3) // 4, dtype=torch.float32, device=xs.device)
+                    setattr(self, ws_slot, ws)
                 self._raise(self.lib.pinn_jet_forward_ws(self.handle, _ptr(params), _ptr(xs), n, dirs, nd, n2, _ptr(ic_streams),
-                                                         float(ic_const), _ptr(out), _ptr(self._fwd_ws), self._fwd_ws.numel() * 4,
-                                                         _stream(xs)))
+                                                         float(ic_const), _ptr(out), _ptr(ws), ws.numel() * 4, _stream(xs)))
             else:
                 self._raise(self.lib.pinn_jet_forward(self.handle, _ptr(params), _ptr(xs), n, dirs, nd, n2, _ptr(ic_streams),
                                                       float(ic_const), _ptr(out), _stream(xs)))
@@ -579,3 +591,49 @@ class Net:
                 int(mode), int(bool(apply_step)), int(self.layout.off_loss if off_loss is None else off_loss), float(t), float(lr),
                 float(tolerance_grad), float(tolerance_change), _ptr(ctrl), ctrl.numel() * 8, _ptr(workspace),
                 workspace.numel() * workspace.element_size(), _stream(params) if stream is None else stream))
+
+    # ---- residual-adaptive resampler (include/pinn.h pinn_resample_points) -----------------------------------------------------------
+    def resample_workspace(self, m, device):
+        """ a workspace for pools of `m` points (float64 tensor; 0 bytes from the library: m outside its range) """
+        need = int(self.lib.pinn_resample_workspace_bytes(int(m)))
+        if need == 0:
+            raise ValueError(f'resample: a pool of {m} points is outside the range of the kernels')
+        return torch.empty(need // 8, dtype=torch.float64, device=device)
+
+    def resample_points(self, pool, r, n_out, power=1, floor=1.0, seed=0, call_index=0, workspace=None, out=None, idx=None,
+                        redraw=False, stream=None):
+        """ n_out rows of `pool` [M, d] drawn with probability proportional to |r|^power + floor * mean(|r|^power) (three launches; Philox
+        keyed by (seed, call_index)). Returns (rows [n_out, d], indices int32 [n_out], workspace); `redraw`: `workspace` already holds
+        the prefix sums of this pool -- fresh uniforms only, one launch (`r`, `power`, `floor` are not looked at). n_out == 0 does
+        nothing at all: the workspace is NOT filled by such a call. Caller-supplied `out` / `idx` must be [n_out, d] / [n_out] on the pool's device. """
+        _check(pool, 'pool'); _check(r, 'r'); _check(out, 'out'); _check(idx, 'idx', torch.int32); _check(workspace, 'workspace', torch.float64)
+        if pool.dim() != 2:
+            raise ValueError('pool must be [M, d]')
+        m, d = pool.shape
+        if not redraw and (r is None or r.numel() != m):
+            raise ValueError(f'r must hold one residual per pool point ({m})')
+        n_out = int(n_out)
+        for t, name, shape in ((r if not redraw else None, 'r', (m,)), (out, 'out', (n_out, d)), (idx, 'idx', (n_out,))):
+            # (the kernels index these by m, n_out and d: a short or foreign buffer would be written past its end)
+            if t is not None and (t.device != pool.device or (tuple(t.shape) != shape and not (name == 'r' and t.numel() == m))):
+                raise ValueError(f'{name} must be a tensor of shape {shape} on {pool.device}, got {tuple(t.shape)} on {t.device}')
+        if workspace is not None and workspace.device != pool.device:
+            raise ValueError(f'workspace must be on {pool.device}, got {workspace.device}')
+        if workspace is None:
+            if redraw:
+                raise ValueError('a redraw needs the workspace a full call has filled')
+            workspace = self.resample_workspace(m, pool.device)
+        if out is None:
+            out = torch.empty((max(int(n_out), 0), d), dtype=torch.float32, device=pool.device)
+        if idx is None:
+            idx = torch.empty(max(int(n_out), 0), dtype=torch.int32, device=pool.device)
+        st = _stream(pool) if stream is None else stream
+        with _on_device(pool):
+            if redraw:
+                self._raise(self.lib.pinn_resample_redraw(_ptr(pool), m, d, int(n_out), int(seed) & (2 ** 64 - 1), int(call_index), _ptr(out),
+                                                          _ptr(idx), _ptr(workspace), workspace.numel() * 8, st))
+            else:
+                self._raise(self.lib.pinn_resample_points(_ptr(pool), _ptr(r.reshape(-1)), m, d, int(power), float(floor), int(n_out),
+                                                          int(seed) & (2 ** 64 - 1), int(call_index), _ptr(out), _ptr(idx), _ptr(workspace),
+                                                          workspace.numel() * 8, st))
+        return out, idx, workspace

@@ -9,10 +9,13 @@ the per-column description (kind, a, b) of include/pinn.h `pinn_sample_points` w
 independent uniform / normal / constant columns -- `Solver.fit` then draws the whole batch with ONE launch of the
 Philox kernel instead of a handful of torch ops per iteration.
 """
+import numbers
+import operator
+
 import numpy as np
 import torch
 
-__all__ = ['Sampler', 'NumpySampler', 'ConstantSampler', 'NS']
+__all__ = ['Sampler', 'NumpySampler', 'ConstantSampler', 'NS', 'ResidualSampler']
 
 _ALIASES = {'u': 'uniform', 'n': 'normal', 'e': 'exponential', 'g': 'gamma'}
 
@@ -146,6 +149,97 @@ class NumpySampler(Sampler):
             if np.ndim(loc) == 0 and np.ndim(scale) == 0:
                 return [(1, float(loc), float(scale))] * self.dim
         return None
+
+
+class ResidualSampler(Sampler):
+    """ residual-based adaptive collocation sampling (RAD: Wu, Zhu, Tan, Kartha, Lu, CMAME 2023; RAR-D with replacement): every `period`
+    iterations `base` draws a pool of `pool * batch_size` candidates, the solver evaluates the equation residual r on them (forward only)
+    and the batch is drawn from the pool with probability proportional to |r|^power / mean(|r|^power) + floor -- on the device, by the
+    resampler kernels of include/pinn.h pinn_resample_points (three launches; one for the iterations that reuse the pool).
+
+    base    any sampler `Solver.fit` accepts; None: U[0, 1) columns. Products of uniform / normal / constant columns are drawn by the
+            Philox kernel, others through `sample_device` / `sample`.
+    pool    candidates per batch point (>= 1);  period: iterations one pool serves (>= 1): pool evaluation amortised over `period` batches
+    power   1 or 2;  floor: the c of RAD (>= 0): 0 is purely residual-proportional, large values approach the base distribution
+    seed    keys the draw stream (per-rank offset under data parallelism, like `NumpySampler(seed=)`); None: the solver's per-fit key
+
+    `Solver.fit(sampler=...)` binds the sampler to the solver; `columns()` is None, so the fit takes the per-iteration path of any
+    external sampler. For inspection: `last_pool` [M, d], `last_residual` [M], `last_indices` int32 [batch] (device tensors of the last
+    call) and `evaluations`, the number of pool evaluations so far. The sampler numbers its draws itself, like a NumpySampler its batches:
+    the count runs on from one fit call to the next (fresh uniforms in every call), only the iteration count that decides when a pool is
+    due starts again at every fit. """
+    MAX_FLOOR = 1e100
+
+    def __init__(self, base=None, pool=4, period=1, power=1, floor=1.0, seed=None):
+        def integer(value, name, meaning):
+            try:
+                if isinstance(value, bool):
+                    raise TypeError
+                value = operator.index(value)           # (Python and numpy integers alike)
+            except TypeError:
+                value = 0
+            if value < 1:
+                raise ValueError(f'ResidualSampler: {name} must be an integer >= 1 ({meaning})')
+            return value
+        pool = integer(pool, f'pool={pool!r}', 'candidates per batch point')
+        period = integer(period, f'period={period!r}', 'iterations per pool')
+        if power not in (1, 2):
+            raise ValueError(f'ResidualSampler: power={power!r} must be 1 or 2')
+        if not (isinstance(floor, numbers.Real) and not isinstance(floor, bool) and 0.0 <= float(floor) <= self.MAX_FLOOR):
+            raise ValueError(f'ResidualSampler: floor={floor!r} must be a number in [0, {self.MAX_FLOOR:g}] (include/pinn.h PINN_RESAMPLE_MAX_FLOOR)')
+        self.base, self.pool, self.period, self.power, self.floor, self.seed = base, pool, period, int(power), float(floor), seed
+        if base is not None:
+            self.dim = base.dim
+        self.solver = None
+        self.evaluations = 0
+        self.last_pool = self.last_residual = self.last_indices = None
+        self._iteration, self._draws, self._workspace, self._pool_size = 0, 0, None, None
+
+    def columns(self):
+        return None
+
+    def seeds(self):
+        return [self.seed]
+
+    def bind_solver(self, solver):
+        """ called by `Solver.fit` at the start of the call: iteration 0 of this fit draws a fresh pool """
+        self.solver = solver
+        self.dim = solver.model.total
+        self._iteration = 0
+
+    def _key(self):
+        solver = self.solver
+        if self.seed is None:
+            if solver._sample_seed is None:
+                solver._new_sample_seed()
+            return solver._sample_seed              # (per fit call, per rank)
+        rank, _ = solver._world()
+        return (self.device_key() + 7919 * rank) & (2 ** 64 - 1)
+
+    def sample_device(self, size, device=None, generator=None):
+        solver = self.solver
+        if solver is None:
+            raise RuntimeError('ResidualSampler draws by the residual of a solver: pass it to Solver.fit(sampler=...) (or call '
+                               'bind_solver(solver)) before sampling')
+        net = solver.model.net
+        m = self.pool * size
+        fresh = self._iteration % self.period == 0 or self._pool_size != m or self.last_pool is None
+        if fresh:
+            self.last_pool = solver._sample(m, self.base)
+            self.last_residual = solver._residual_device(self.last_pool)
+            self.evaluations += 1
+            self._pool_size = m
+            if self._workspace is None or self._workspace.device != self.last_pool.device or \
+                    self._workspace.numel() * 8 < int(net.lib.pinn_resample_workspace_bytes(m)):
+                self._workspace = net.resample_workspace(m, self.last_pool.device)
+        xs, self.last_indices, _ = net.resample_points(self.last_pool, self.last_residual, size, self.power, self.floor, self._key(),
+                                                       self._draws, workspace=self._workspace, redraw=not fresh)
+        self._draws += 1
+        self._iteration += 1
+        return xs
+
+    def sample(self, size):
+        return self.sample_device(size).detach().cpu().numpy().astype(np.float64)
 
 
 NS = NumpySampler

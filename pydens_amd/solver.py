@@ -1225,6 +1225,8 @@ class Solver:
         local_batch = batch_size // world + (1 if rank < batch_size % world else 0)
         self._global_batch = batch_size
         self._new_sample_seed()
+        if hasattr(sampler, 'bind_solver'):         # (ResidualSampler: it asks this solver for the residual of its candidate pool)
+            sampler.bind_solver(self)
         lay = model.net.layout
         history = torch.zeros(niters, dtype=torch.float32, device=self.device)
         done = [0]
@@ -1548,6 +1550,75 @@ class Solver:
             self.grads[lay.off_loss] = loss.detach()
         finally:
             model.grad_sink = None
+            self._imap = UNSET
+
+    RESIDUAL_SLICE = 1 << 20    # points per forward pass of `residual`: bounds the stream buffers ([streams, N] floats) of a large pool
+
+    def residual(self, *xs):
+        """ the value of the equation callable at the given points with the current parameters -> ndarray [N, 1]; arguments as for
+        `predict`. Forward only: the jet kernels hand the derivative streams to the equation (the forward half of the generic step, so
+        every equation `fit` accepts is served, lowered to a residual program or not). Nothing is written to `grads`, no `.grad` is
+        touched, the launch graphs of a fit stay as they are, the model's train / eval mode is restored. """
+        with self._device_guard():
+            pts = self.reshape_and_concat(xs, device=self.device).contiguous()
+            # the traces as `fit` builds them (a re-assigned equation, a changed closure constant); the validation draws random points:
+            # on a fork of the generators, so that a later fit samples what it would have sampled without this call
+            devices = [self.device] if self.device.type == 'cuda' else []
+            with torch.random.fork_rng(devices=devices):
+                self._refresh_traces(set())
+            return self._residual_device(pts).view(-1, 1).cpu().numpy()
+
+    def _residual_device(self, pts):
+        """ `residual` on a device tensor [N, total] -> device tensor [N]; no host copy, no synchronisation (ResidualSampler) """
+        model = self.model
+        was_training = model.training
+        model.eval()
+        try:
+            n = pts.shape[0]
+            if n == 1 and model.initial_condition is not None and model.ic_constant is None:
+                # (`_ic_streams` takes a callable IC that returns ONE value for a constant and skips its derivative streams: a lone
+                #  point is evaluated as two copies of itself)
+                return self._residual_slice(pts.repeat(2, 1))[:1]
+            if n <= self.RESIDUAL_SLICE:
+                return self._residual_slice(pts)
+            out = torch.empty(n, dtype=torch.float32, device=self.device)
+            for lo in range(0, n, self.RESIDUAL_SLICE):
+                out[lo:lo + self.RESIDUAL_SLICE] = self._residual_slice(pts[lo:lo + self.RESIDUAL_SLICE])
+            return out
+        finally:
+            model.train(was_training)
+
+    def _residual_slice(self, xs):
+        """ the forward half of `_generic_step` on one slice of points: jet_forward per direction group, IC streams, the input map of a
+        custom forward(), the equation. Equations that differentiate inside their torch code run with grad enabled and are detached.
+        Nested-skip nets need forward scratch: a buffer of this method's own (engine.Net.jet_forward `ws_slot`), never the step's, whose
+        address a recorded launch graph of the generic step carries. """
+        model, spec = self.model, self.spec
+        with_grad = bool(self.needs_x_grad)
+        kpts = xs
+        try:
+            if self.custom_forward:
+                self._imap = self._input_map(xs)
+                if self._imap is not None:
+                    kpts = self._imap[0]
+            with torch.no_grad():
+                if len(spec.groups) == 1:
+                    leaf = model.net.jet_forward(model.flat, kpts, spec.dir_cols, spec.n2p, ic_const=model.kernel_ic_const(), ws_slot='_residual_fwd_ws')
+                else:
+                    leaf = torch.empty((spec.n_streams, xs.shape[0]), dtype=torch.float32, device=self.device)
+                    for num, (dirs_g, n2g, idx) in enumerate(spec.groups):
+                        part = model.net.jet_forward(model.flat, kpts, dirs_g, n2g, ic_const=model.kernel_ic_const(), ws_slot='_residual_fwd_ws')
+                        leaf.index_copy_(0, self._group_rows(num, idx), part)
+            ic_streams = None
+            if model.initial_condition is not None and model.ic_constant is None and not self.custom_forward:
+                with torch.enable_grad():           # (the IC's derivative streams are torch autograd over the callable)
+                    ic_streams = self._ic_streams(xs, create_graph=with_grad)
+            with (torch.enable_grad() if with_grad else torch.no_grad()):
+                if with_grad:
+                    leaf.requires_grad_()
+                r = self._eval_equation(leaf, xs, ic_streams, requires_grad=with_grad)
+            return r.detach().reshape(-1).float()
+        finally:
             self._imap = UNSET
 
     def predict(self, *xs):
