@@ -108,9 +108,9 @@ class FlatOptimizer:
         self.calls = []             # (step count at its start, set of unreached offsets) per fit call this optimizer served
 
     def refresh(self, unreached=()):
-        """ unreached: offsets of scalars (log_scale, V(...) slots) the loss terms of the coming fit call do not reach: the reference's backward
-        leaves them without a gradient and Adam SKIPS them -- moments, step count and value stay. With fresh moments a zero gradient does the
-        same; a reused optimizer (`optimizer=None`) would walk on along the old momentum (Solver._unreached_scalars). """
+        """ unreached: offsets of entries (log_scale, V(...) slots, the output bias) the loss terms of the coming fit call do not reach: the
+        reference's backward leaves them without a gradient and torch's optimizers SKIP them -- moments, step count and value stay. Reached with
+        a gradient that happens to be zero is something else: such an entry is stepped (Solver._unreached_scalars decides from the graph). """
         new = self.model.trainable_mask()
         if self.members is None:
             # (a buffer of the MODEL, like the mask and the moments: a fresh allocation per fit call shifted what the allocator hands the rest
@@ -340,7 +340,7 @@ class TorchOptimizerAdapter:
         self.opt = getattr(torch.optim, flat.name)(self.params, lr=flat.lr, **flat.torch_kwargs)
         first, second = flat.state_keys()
         for p in self.params:
-            steps = flat.steps_of(p.storage_offset()) if p.numel() == 1 else flat.t
+            steps = flat.steps_of(p.storage_offset())       # (a fit call reaches a parameter as a whole: its first entry speaks for all)
             if steps > 0:
                 view = lambda buf: buf.as_strided(tuple(p.shape), tuple(p.stride()), p.storage_offset()).clone()
                 state = {} if flat.name == 'SGD' else {'step': torch.tensor(float(steps))}
@@ -352,8 +352,11 @@ class TorchOptimizerAdapter:
                     self.opt.state[p] = state
         return self
 
-    def refresh(self):
-        pass
+    def refresh(self, unreached=()):
+        """ unreached: offsets in the flat buffer the loss terms of the coming fit call do not reach (Solver._unreached_scalars, as for
+        FlatOptimizer.refresh): a parameter that starts at one of them is bound without a gradient, and torch skips it """
+        unreached = set(unreached)
+        self.unreached = {id(p) for p in self.params if p.storage_offset() in unreached}
 
     @property
     def needs_closure(self):
@@ -390,16 +393,12 @@ class TorchOptimizerAdapter:
     def _bind(self, grads, contiguous=False):
         # Parameters WITHOUT a gradient are skipped by torch's optimizers -- no weight decay, no momentum step, no step count -- and the
         # reference's backward leaves `.grad = None` on (a) a parameter frozen since this optimizer was built (`fit(optimizer=None)` after
-        # freeze_trainable) and (b) a scalar the loss of this call does not reach: `log_scale` without an initial condition, a V(...) of the
-        # equation in a constraint-only call (round 6's fit-sequence fuzz: AdamW decayed such a variable). The kernels deliver a flat buffer
-        # with an exact 0.0 there; a one-entry parameter whose gradient is exactly zero is taken for unreached (one small read-back per step).
-        scalars = [p for p in self.params if p.numel() == 1 and p.requires_grad]
-        zero = set()
-        if scalars:
-            values = torch.stack([grads[p.storage_offset()] for p in scalars]).tolist()
-            zero = {id(p) for p, v in zip(scalars, values) if v == 0.0}
+        # freeze_trainable) and (b) a parameter the loss of this call does not reach: `log_scale` without an initial condition, a V(...) of the
+        # equation in a constraint-only call, the output bias under a residual of derivatives alone. Which those are is a property of the
+        # graph, settled once per fit call (`refresh`); a reached parameter whose gradient is zero gets that zero tensor and is stepped.
+        skipped = getattr(self, 'unreached', ())
         for p in self.params:
-            reached = p.requires_grad and id(p) not in zero
+            reached = p.requires_grad and id(p) not in skipped
             p.grad = grads.as_strided(tuple(p.shape), tuple(p.stride()), p.storage_offset()) if reached else None
             if contiguous and reached:
                 p.grad = p.grad.contiguous()
@@ -1145,25 +1144,67 @@ class Solver:
         self._all_reduce(stream)
         self.optimizer.step(self.grads, loss_out=loss_out, stream=stream)
 
-    def _unreached_scalars(self, offsets, loss_terms, nums_constraints, criterion):
-        """ offsets of the trainable scalars (log_scale, V(...) slots) that the loss of these terms does not depend on -- the equation's
-        variable in a constraint-only call, log_scale without an initial condition: one dry evaluation of the terms on a few random points
-        through the generic step (torch autograd tells), read back once per fit call of a model with variables (FlatAdam.refresh). """
-        model = self.model
+    def _unreached_scalars(self, loss_terms, nums_constraints, criterion):
+        """ offsets in the flat buffer of what the loss of these terms does not REACH, although it is trainable: log_scale without an initial
+        condition, a V(...) of the equation in a constraint-only call, the output bias under a residual that holds derivatives of the
+        network alone. The reference's backward leaves those without a gradient and torch's optimizers skip them (no decay, no momentum
+        step, no step count); everything else is stepped, also where its gradient is zero -- a variable behind a zero co-factor, a
+        coefficient that is switched on elsewhere in the domain, a sum that cancels on one batch. So the decision is taken from the GRAPH,
+        never from a value: one dry evaluation of the terms through the generic step per fit call, asked for connectivity only
+          * V(...):      `.grad is None` after the backward of the dry evaluation (all entries of a vector variable together);
+          * log_scale:   reached exactly when an initial condition is bound (a model with its own forward(): torch autograd tells);
+          * output bias: reached when the network's VALUE is -- through a constraint term, the equation's u, or a derivative stream along
+                         a direction in which the ansatz factor varies (boundary binding: spatial columns; initial condition: time).
+        The points of the dry evaluation are five U[0, 1) draws from a generator of its own: connectivity does not depend on where the
+        terms are evaluated (nor on the sampler's domain), and the call's sampler is not asked for a batch it would then be short of.
+        A dry evaluation that fails (the fit itself will say why) leaves everything reached. """
+        model, lay = self.model, self.model.net.layout
         if not any(term == 'equation' or 'constraint' in term for term in loss_terms):
             return []
+        probe = {}
         keep = self.grads.clone()
         try:
             gen = torch.Generator(device=self.device)           # (its own stream: the solver's sampling seeds come from torch's global one)
             gen.manual_seed(5)
             self._generic_step(torch.rand((5, model.total), device=self.device, generator=gen), loss_terms,
-                               [num for num in nums_constraints if num < len(self.constraints)], criterion, 1)
-            values = self.grads[torch.tensor(offsets, device=self.device)].tolist()
-        except Exception:                                       # (an equation that cannot be evaluated on U[0, 1) points: the fit itself will say;
-            return []                                           #  every scalar counts as reached, the behaviour before this check existed)
+                               [num for num in nums_constraints if num < len(self.constraints)], criterion, 1, probe=probe)
+        except Exception:
+            return []
         finally:
             self.grads.copy_(keep)
-        return [off for off, v in zip(offsets, values) if v == 0.0]
+        unreached = []
+        if not (probe['log_scale'] if self.custom_forward else model.initial_condition is not None):
+            unreached.append(lay.off_log_scale)
+        for name, (off, n) in model.variables.items():
+            if name not in probe['variables']:
+                unreached.extend(range(off, off + n))
+        if not self._value_reached(probe):
+            bias = [m for m in model.conv_block][-1].bias
+            unreached.extend(range(bias.storage_offset(), bias.storage_offset() + bias.numel()))
+        return unreached
+
+    def _value_reached(self, probe):
+        """ does the loss of the dry evaluation hold the network's value (and with it the output bias, which the derivatives of the network
+        do not hold)? `probe['streams']`: per kernel stream, whether the backward gave it a gradient. Stream 0 is u; the derivative streams
+        along direction k hold the value through the product rule where the ansatz factor varies along k. """
+        model, spec = self.model, self.spec
+        if probe.get('value') or not probe['streams']:
+            return bool(probe.get('value'))
+        streams = probe['streams']
+        if streams[0]:
+            return True
+        varying = set()
+        if not self.custom_forward:             # (its ansatz is torch code around the value stream: autograd has told through stream 0)
+            if model.boundary_condition is not None:
+                varying |= set(range(model.ndims_spatial))
+            if model.initial_condition is not None:
+                varying.add(model.ndims - 1)
+        for k, direction in enumerate(spec.dirs):
+            rows = [1 + k] + [base + k for base, count in ((1 + spec.nd, spec.n2), (1 + spec.nd + spec.n2, spec.n3),
+                                                           (1 + spec.nd + spec.n2 + spec.n3, spec.n4)) if k < count]
+            if any(streams[row] for row in rows) and any(c in varying for c, _ in trace.dir_weights(direction)):
+                return True
+        return False
 
     def fit(self, niters, batch_size, sampler=None, loss_terms='equation', optimizer='Adam',
             criterion=nn.MSELoss(), lr=0.005, **kwargs):
@@ -1195,16 +1236,20 @@ class Solver:
         nums_constraints = [int(term.replace('constraint', '').replace('_', ''))
                             for term in loss_terms if 'constraint' in term]
         self._refresh_traces(set(nums_constraints))
-        if isinstance(self.optimizer, FlatOptimizer) and (model.variables or not isinstance(self.optimizer, FlatAdam)):
-            # (trainable V(...) scalars: which of them the terms of THIS call reach decides what torch's Adam does with them; one dry
-            #  evaluation per fit call. Without variables nothing changes from call to call: log_scale is reached iff there is an IC --
-            #  which plain Adam need not know, a zero gradient on fresh moments moves nothing; weight decay would move it, so the other
-            #  rules always ask)
-            lay = model.net.layout
-            scalars = [lay.off_log_scale] + [off + i for off, n in model.variables.values() for i in range(n)]
-            self.optimizer.refresh(self._unreached_scalars(scalars, loss_terms, nums_constraints, criterion))
-            if optimizer is None and self.optimizer.lagging(scalars):
-                self.optimizer = TorchOptimizerAdapter.continuing(self.optimizer)
+        if isinstance(self.optimizer, TorchOptimizerAdapter) or model.variables or not isinstance(self.optimizer, FlatAdam):
+            # (what the terms of THIS call reach decides what torch's optimizers do with a parameter: one dry evaluation per fit call, asked
+            #  for graph connectivity -- _unreached_scalars. Plain Adam on a model without variables need not know: nothing changes from call
+            #  to call there, and its update of an entry that never has a gradient is no move at all; weight decay would move it, and a
+            #  variable's reach differs from call to call, so every other case asks)
+            unreached = self._unreached_scalars(loss_terms, nums_constraints, criterion)
+            self.optimizer.refresh(unreached)
+            if optimizer is None and isinstance(self.optimizer, FlatOptimizer):
+                lay = model.net.layout
+                bias = [m for m in model.conv_block][-1].bias
+                scalars = [lay.off_log_scale, bias.storage_offset()] + [off + i for off, n in model.variables.values() for i in range(n)]
+                if self.optimizer.lagging(scalars):
+                    self.optimizer = TorchOptimizerAdapter.continuing(self.optimizer)
+                    self.optimizer.refresh(unreached)
         else:
             self.optimizer.refresh()
         self._constraints_seen |= {num for num in nums_constraints if num < len(self.constraints)}
@@ -1477,7 +1522,10 @@ class Solver:
             self._constraint_step(num, world, accumulate=not first)
             first = False
 
-    def _generic_step(self, xs, loss_terms, nums_constraints, criterion, world):
+    def _generic_step(self, xs, loss_terms, nums_constraints, criterion, world, probe=None):
+        """ probe: a dict -- the step is a DRY evaluation that is asked which parts of the graph the loss reaches (_unreached_scalars): every
+        kernel stream is a leaf of its own, the backward stops at the streams, and `probe` receives 'streams' (per stream: did it get a
+        gradient), 'variables' (names of the V(...) that did), 'log_scale', 'value' (a constraint term's model value did) """
         model, spec = self.model, self.spec
         lay = model.net.layout
         self.grads.zero_()
@@ -1508,6 +1556,8 @@ class Solver:
                         part = model.net.jet_forward(model.flat, kpts, dirs_g, n2g, ic_const=model.kernel_ic_const())
                         leaf.index_copy_(0, self._group_rows(num, idx), part)
                     leaf.requires_grad_()
+                if probe is not None:
+                    leaf = [row.detach().requires_grad_() for row in leaf.detach().unbind(0)]
                 ic_streams = None
                 if model.initial_condition is not None and model.ic_constant is None and not self.custom_forward:
                     ic_streams = self._ic_streams(xs, create_graph=True)       # (custom forward(): the IC is torch code of the model)
@@ -1516,14 +1566,21 @@ class Solver:
                 loss = loss + (term if world == 1 else term * w_eq)
 
             def _forward(*pts):                                                          # :451-454
-                return model(self._points_on_device(pts))
+                out = model(self._points_on_device(pts))
+                if probe is not None and out.requires_grad:
+                    out.register_hook(lambda g: probe.__setitem__('value', True))
+                return out
 
             cols = [xs[:, c:c + 1] for c in range(model.total)]
             for num in nums_constraints:                                                  # :456-457
                 term = criterion(self.ctx.run(self.constraints[num], _forward, *cols), torch.zeros(1, device=self.device))
                 loss = loss + (term if world == 1 else term * w_con)
             loss.backward()
-            if leaf is not None and leaf.grad is not None:
+            if probe is not None:
+                probe['streams'] = [] if leaf is None else [row.grad is not None for row in leaf]
+                probe['variables'] = {name for name in model.variables if getattr(model, name).grad is not None}
+                probe['log_scale'] = model.log_scale.grad is not None
+            elif leaf is not None and leaf.grad is not None:
                 if len(spec.groups) == 1:
                     ws = model.workspace(xs.shape[0], spec.nd, spec.n2p)
                     model.net.jet_backward(model.flat, kpts, leaf.grad.contiguous(), self.grads, ws, spec.dir_cols, spec.n2p,
