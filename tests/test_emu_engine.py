@@ -1284,7 +1284,8 @@ def test_hidden_width_512_matches_the_oracle(pa, emu_lib, which):
 
 def _wide512_case(pa, which, solver_kwargs, n):
     """ round 6: widths 257 .. 512 run on kernels of their own -- S <= 3 streams per call (LDS), anything larger in direction groups, eight
-    bias-gradient rows, the streamed weight-gradient kernel in four 256 x 256 block passes """
+    bias-gradient rows, the streamed weight-gradient kernel in four 256 x 256 block passes
+    (the loops of that path -- second tiles, ragged tiles, all 512 units, eight layers, every instantiation: tests/test_width_512.py) """
     from oracle import pinn_oracle as po
     torch.manual_seed(53)
     eq_o, kw, path = _wide512_problems(po.D, torch, which)

@@ -1116,7 +1116,8 @@ def test_evolution_shape_in_x_t_on_the_two_team_kernels(pa, which):
 
 @pytest.mark.parametrize('which', ['ode_fused', 'poisson_groups', 'heat_sigmoid', 'advection_breadth'])
 def test_hidden_width_512_on_the_gpu(pa, which):
-    """ round 6: hidden widths 257 .. 512 (S <= 3 streams per kernel call, direction groups beyond, block passes of the weight-gradient kernel) """
+    """ round 6: hidden widths 257 .. 512 (S <= 3 streams per kernel call, direction groups beyond, block passes of the weight-gradient kernel).
+    (The loops of that path -- second tiles, ragged tiles, all 512 units, eight layers, every instantiation: tests/test_width_512.py.) """
     import test_emu_engine as te
     te._wide512_case(pa, which, {}, 4000)
 
