@@ -359,6 +359,20 @@ int pinn_fit_steps_optim_graph(pinn_t* net, const pinn_residual_t* residual, flo
                                const uint8_t* mask, int32_t* step_ptr, int32_t step0, const pinn_optim_t* opt,
                                float* loss_history, int32_t k_steps, void* workspace, size_t workspace_bytes, void* ctrl,
                                size_t ctrl_bytes, void* stream);
+/* pinn_fit_steps_optim_graph under a learning-rate schedule (`torch.optim.lr_scheduler`: the loop `opt.step(); sched.step()` around
+ * model_torch.py:461). lr_steps is HOST memory, k_steps finite rates >= 0 that the caller's scheduler produced: iteration k of the chunk
+ * is the update pinn_residual_optim_step performs with opt->lr = lr_steps[k] -- bit for bit on the eager loop and on the launch-graph form;
+ * on the one-launch form of narrow nets within the bound that form has against the eager loop. The rates reach the kernels through the
+ * control block, per iteration like Adam's bias corrections (step_size[k] from lr_steps[k]; lr[k] for SGD and RMSprop; decay[k] =
+ * 1 - lr_steps[k] * weight_decay for AdamW, formed in double from the decimal values like every other derived scalar). The launch-graph
+ * cache key of a call with lr_steps leaves opt->lr out: chunks that differ only in their rates replay one recording. opt->lr itself must
+ * still be valid; it is used nowhere. lr_steps == NULL is pinn_fit_steps_optim_graph. The array is read before the call returns. */
+int pinn_fit_steps_optim_sched(pinn_t* net, const pinn_residual_t* residual, float* params, float* xs, int64_t n_points,
+                               const int* kind, const float* a, const float* b, uint64_t seed, uint64_t call_index0,
+                               const int* dir_cols, int nd, int n2, float ic_const, float* grads, float* exp_avg, float* exp_avg_sq,
+                               const uint8_t* mask, int32_t* step_ptr, int32_t step0, const pinn_optim_t* opt,
+                               float* loss_history, int32_t k_steps, void* workspace, size_t workspace_bytes, void* ctrl,
+                               size_t ctrl_bytes, void* stream, const float* lr_steps);
 
 /* The reference's fit loop (model_torch.py:426-464) for the common case -- on-device column sampler, one equation term on the
  * fused path, Adam -- as ONE call that enqueues `k_steps` iterations: iteration k draws batch `call_index0 + k` into `xs`

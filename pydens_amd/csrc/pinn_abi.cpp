@@ -7,6 +7,7 @@
 #include "pinn_lbfgs_kernels.h"
 
 #include <atomic>
+#include <cfloat>
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
@@ -393,6 +394,36 @@ static int optim_prepare(const pinn_optim_t* o, PinnOptK* k) {
 static void optim_scalars(const PinnOptK& k, double step, float* step_size, float* bc2_sqrt) {
     *step_size = 0.0f; *bc2_sqrt = 1.0f;
     if (k.rule == PINN_OPT_ADAM || k.rule == PINN_OPT_ADAMW) pinn_adam_scalars(step, k.lr, k.b1, k.b2, step_size, bc2_sqrt);
+}
+
+// the rule `k` at the learning rate of ONE iteration of a schedule: what optim_prepare makes of the same pinn_optim_t with `lr` in place
+// of its own (the rate itself and AdamW's 1 - lr * weight_decay from the widened doubles; nothing else derives from the rate)
+static PinnOptK optim_at_rate(const PinnOptK& k, float lr) {
+    PinnOptK r = k;
+    r.lr = lr;
+    if (k.rule == PINN_OPT_ADAMW) r.decay = (float)(1.0 - widen(lr) * widen(k.wd));
+    return r;
+}
+
+// lr_steps of pinn_fit_steps_optim_sched: k_steps finite, non-negative rates in host memory (NULL: the constant rate of the struct)
+static int check_lr_steps(const float* lr_steps, int32_t k_steps) {
+    for (int32_t k = 0; lr_steps && k < k_steps; ++k)
+        if (!(lr_steps[k] >= 0.0f) || !(lr_steps[k] <= FLT_MAX)) return fail("lr_steps[%d]: invalid learning rate %g", (int)k, (double)lr_steps[k]);
+    return 0;
+}
+
+// the control block of a chunk as pinn_fit_ctrl_kernel takes it: per iteration the bias corrections, the learning rate and what
+// derives from it -- the very numbers the eager loop hands its launches by value
+static void fit_ctrl_fill(PinnFitCtrlArgs* ca, uint64_t call_index0, float* loss_history, int32_t step0, uint64_t seed, const PinnOptK& opt,
+                          const float* lr_steps, int32_t k_steps) {
+    ca->c.call_index0 = call_index0; ca->c.loss_base = loss_history; ca->c.step0 = step0; ca->c.pad = 0;
+    ca->c.k0 = (unsigned)(seed & 0xffffffffull); ca->c.k1 = (unsigned)(seed >> 32);
+    for (int k = 0; k < PINN_FIT_CHUNK_MAX; ++k) {
+        const PinnOptK ok = (lr_steps && k < k_steps) ? optim_at_rate(opt, lr_steps[k]) : opt;
+        ca->c.step_size[k] = 0.0f; ca->c.bc2_sqrt[k] = 1.0f;
+        if (k < k_steps) optim_scalars(ok, (double)(step0 + k), &ca->c.step_size[k], &ca->c.bc2_sqrt[k]);
+        ca->c.lr[k] = ok.lr; ca->c.decay[k] = ok.decay;
+    }
 }
 
 // which form of the reduction the last launch_reduce took (pinn_last_reduce_kernel_name)
@@ -1178,9 +1209,11 @@ static int fit_steps_impl(pinn_t* net, const pinn_residual_t* residual, float* p
                           const int* kind, const float* a, const float* b, uint64_t seed, uint64_t call_index0,
                           const int* dir_cols, int nd, int n2, float ic_const, float* grads, float* exp_avg, float* exp_avg_sq,
                           const uint8_t* mask, int32_t* step_ptr, int32_t step0, const PinnOptK& opt,
-                          float* loss_history, int32_t k_steps, void* workspace, size_t workspace_bytes, void* stream) {
+                          float* loss_history, int32_t k_steps, void* workspace, size_t workspace_bytes, void* stream,
+                          const float* lr_steps = nullptr) {
     if (!net || !xs || !loss_history) return fail("null argument");
     if (k_steps < 0 || step0 < 1) return fail("k_steps must be >= 0 and step0 >= 1");
+    if (check_lr_steps(lr_steps, k_steps)) return 1;
     // K iterations of the reference's fit loop (model_torch.py:426-464) enqueued by ONE call: sample, fused step, Adam. Nothing
     // here waits for the device; the arguments that change from one iteration to the next (Philox batch counter, Adam step,
     // slot of the loss history) travel by value, so a launch graph would have to be re-instantiated per iteration anyway
@@ -1194,9 +1227,10 @@ static int fit_steps_impl(pinn_t* net, const pinn_residual_t* residual, float* p
         if (k == 0 || !hand_over) rc = pinn_sample_points(xs, n_points, net->lay.d, kind, a, b, seed, call_index0 + (uint64_t)k, stream);
         if (rc) break;
         if (hand_over && k + 1 < k_steps) { next.call = call_index0 + (uint64_t)k + 1; g_fit_next = next; }
+        // (a schedule: iteration k is the step of pinn_residual_optim_step with opt->lr = lr_steps[k])
         rc = residual_optim_step(net, residual, params, xs, n_points, dir_cols, nd, n2, nullptr, ic_const, grads, exp_avg,
-                                 exp_avg_sq, mask, step_ptr, step0 + k, opt, loss_history + k, workspace,
-                                 workspace_bytes, stream);
+                                 exp_avg_sq, mask, step_ptr, step0 + k, lr_steps ? optim_at_rate(opt, lr_steps[k]) : opt, loss_history + k,
+                                 workspace, workspace_bytes, stream);
         g_fit_next.n = 0;
     }
     return rc;
@@ -1246,9 +1280,10 @@ static int fit_steps_graph_impl(pinn_t* net, const pinn_residual_t* residual, fl
                                 const int* dir_cols, int nd, int n2, float ic_const, float* grads, float* exp_avg, float* exp_avg_sq,
                                 const uint8_t* mask, int32_t* step_ptr, int32_t step0, const PinnOptK& opt,
                                 float* loss_history, int32_t k_steps, void* workspace, size_t workspace_bytes, void* ctrl,
-                                size_t ctrl_bytes, void* stream) {
+                                size_t ctrl_bytes, void* stream, const float* lr_steps = nullptr) {
     if (!net || !residual || !xs || !loss_history || !kind || !a || !b || !dir_cols) return fail("null argument");
     if (k_steps < 0 || step0 < 1) return fail("k_steps must be >= 0 and step0 >= 1");
+    if (check_lr_steps(lr_steps, k_steps)) return 1;
     // narrow nets, batches of a few tiles: the whole chunk -- any length up to PINN_FIT_CHUNK_MAX -- as ONE launch (pinn_fit_kernel.h);
     // the eager loop's trajectory to fp32 round-off
     if (net->fit_persistent && net->lay.hp <= 32 && ctrl && ctrl_bytes >= sizeof(PinnFitCtrl) && k_steps >= 1 && k_steps <= PINN_FIT_CHUNK_MAX &&
@@ -1257,12 +1292,7 @@ static int fit_steps_graph_impl(pinn_t* net, const pinn_residual_t* residual, fl
         if (fit_next_spec(net, xs, n_points, kind, a, b, seed, &spec_probe) == 0) {
             PinnFitCtrl* dctrl = reinterpret_cast<PinnFitCtrl*>(ctrl);
             PinnFitCtrlArgs ca;
-            ca.c.call_index0 = call_index0; ca.c.loss_base = loss_history; ca.c.step0 = step0; ca.c.pad = 0;
-            ca.c.k0 = (unsigned)(seed & 0xffffffffull); ca.c.k1 = (unsigned)(seed >> 32);
-            for (int k = 0; k < PINN_FIT_CHUNK_MAX; ++k) {
-                ca.c.step_size[k] = 0.0f; ca.c.bc2_sqrt[k] = 1.0f;
-                if (k < k_steps) optim_scalars(opt, (double)(step0 + k), &ca.c.step_size[k], &ca.c.bc2_sqrt[k]);
-            }
+            fit_ctrl_fill(&ca, call_index0, loss_history, step0, seed, opt, lr_steps, k_steps);
             memset(&g_fit_persist, 0, sizeof(g_fit_persist));
             PinnFitP& P = g_fit_persist.p;
             P.ctrl = dctrl; P.k_steps = k_steps; P.xs = xs; P.n = (long long)n_points; P.spec = spec_probe.spec;
@@ -1286,13 +1316,13 @@ static int fit_steps_graph_impl(pinn_t* net, const pinn_residual_t* residual, fl
     }
 #ifdef PINN_EMU
     return fit_steps_impl(net, residual, params, xs, n_points, kind, a, b, seed, call_index0, dir_cols, nd, n2, ic_const, grads, exp_avg,
-                          exp_avg_sq, mask, step_ptr, step0, opt, loss_history, k_steps, workspace, workspace_bytes, stream);
+                          exp_avg_sq, mask, step_ptr, step0, opt, loss_history, k_steps, workspace, workspace_bytes, stream, lr_steps);
 #else
     // the graph pays where launch gaps are a visible share of an iteration; chunks that do not qualify run the eager loop
     // (only whole chunks: the tail of a fit would capture a graph of its own that nothing replays)
     if (k_steps != PINN_FIT_CHUNK_MAX || !ctrl || ctrl_bytes < sizeof(PinnFitCtrl) || g_profile || g_phase_prof)
         return fit_steps_impl(net, residual, params, xs, n_points, kind, a, b, seed, call_index0, dir_cols, nd, n2, ic_const, grads, exp_avg,
-                              exp_avg_sq, mask, step_ptr, step0, opt, loss_history, k_steps, workspace, workspace_bytes, stream);
+                              exp_avg_sq, mask, step_ptr, step0, opt, loss_history, k_steps, workspace, workspace_bytes, stream, lr_steps);
     // everything the captured launches carry BY VALUE or by address (the per-iteration values travel through the control block)
     unsigned long long key[4] = {14695981039346656037ull, 14695981039346656037ull ^ 1, 14695981039346656037ull ^ 2, 14695981039346656037ull ^ 3};
     key_mix(key, residual, sizeof(*residual));
@@ -1303,8 +1333,12 @@ static int fit_steps_graph_impl(pinn_t* net, const pinn_residual_t* residual, fl
                               net->prepass_in_kernel, (long long)net->wgx_chunk_bytes};
     key_mix(key, ints, sizeof(ints));
     const float flts[] = {ic_const, residual->crit_param};
-    // (the update rule with its hyper-parameters: the reductions of the recorded chunk carry it by value)
-    key_mix(key, &opt, sizeof(opt));
+    // (the update rule with its hyper-parameters: the reductions of the recorded chunk carry it by value. Under a control block they
+    //  read the learning rate and what derives from it -- step_size, decay -- from the block, never from that copy: a call with a
+    //  schedule keys on the rule WITHOUT them, so chunks that differ only in their rates replay one recording)
+    PinnOptK key_opt = opt;
+    if (lr_steps) { key_opt.lr = 0.0f; key_opt.decay = 0.0f; key_opt.pad = 1; }
+    key_mix(key, &key_opt, sizeof(key_opt));
     // (the criterion is part of `residual`, hashed above; named here once more so that the key does not depend on where the fields sit)
     const int crit_key[] = {residual->criterion, residual->crit_sum};
     key_mix(key, crit_key, sizeof(crit_key));
@@ -1323,7 +1357,7 @@ static int fit_steps_graph_impl(pinn_t* net, const pinn_residual_t* residual, fl
         // the first chunk of a configuration runs eagerly AND is followed by the capture of the graph the next chunks replay
         const int rc = fit_steps_impl(net, residual, params, xs, n_points, kind, a, b, seed, call_index0, dir_cols, nd, n2, ic_const, grads,
                                       exp_avg, exp_avg_sq, mask, step_ptr, step0, opt, loss_history, k_steps, workspace,
-                                      workspace_bytes, stream);
+                                      workspace_bytes, stream, lr_steps);
         if (rc) return rc;
         hipGraph_t graph = nullptr;
         // capture happens on a stream of the library's own (torch's current stream is usually the legacy default stream, which cannot
@@ -1365,12 +1399,7 @@ static int fit_steps_graph_impl(pinn_t* net, const pinn_residual_t* residual, fl
         return 0;                   // (this chunk ran eagerly above)
     }
     PinnFitCtrlArgs ca;
-    ca.c.call_index0 = call_index0; ca.c.loss_base = loss_history; ca.c.step0 = step0; ca.c.pad = 0;
-    ca.c.k0 = (unsigned)(seed & 0xffffffffull); ca.c.k1 = (unsigned)(seed >> 32);
-    for (int k = 0; k < PINN_FIT_CHUNK_MAX; ++k) {
-        ca.c.step_size[k] = 0.0f; ca.c.bc2_sqrt[k] = 1.0f;
-        if (k < k_steps) optim_scalars(opt, (double)(step0 + k), &ca.c.step_size[k], &ca.c.bc2_sqrt[k]);
-    }
+    fit_ctrl_fill(&ca, call_index0, loss_history, step0, seed, opt, lr_steps, k_steps);
     hipLaunchKernelGGL(pinn_fit_ctrl_kernel, dim3(1), dim3(128), 0, hs, dctrl, ca);
     if (hipGetLastError() != hipSuccess) return fail("control-block launch failed");
     if (hipGraphLaunch((hipGraphExec_t)net->fit_graph_exec, hs) != hipSuccess) return fail("hipGraphLaunch failed");
@@ -1401,6 +1430,19 @@ int pinn_fit_steps_optim_graph(pinn_t* net, const pinn_residual_t* residual, flo
     return fit_steps_graph_impl(net, residual, params, xs, n_points, kind, a, b, seed, call_index0, dir_cols, nd, n2, ic_const, grads, exp_avg,
                                 exp_avg_sq, mask, step_ptr, step0, k, loss_history, k_steps, workspace, workspace_bytes, ctrl, ctrl_bytes,
                                 stream);
+}
+
+int pinn_fit_steps_optim_sched(pinn_t* net, const pinn_residual_t* residual, float* params, float* xs, int64_t n_points,
+                               const int* kind, const float* a, const float* b, uint64_t seed, uint64_t call_index0,
+                               const int* dir_cols, int nd, int n2, float ic_const, float* grads, float* exp_avg, float* exp_avg_sq,
+                               const uint8_t* mask, int32_t* step_ptr, int32_t step0, const pinn_optim_t* opt,
+                               float* loss_history, int32_t k_steps, void* workspace, size_t workspace_bytes, void* ctrl,
+                               size_t ctrl_bytes, void* stream, const float* lr_steps) {
+    PinnOptK k;
+    if (optim_prepare(opt, &k)) return 1;
+    return fit_steps_graph_impl(net, residual, params, xs, n_points, kind, a, b, seed, call_index0, dir_cols, nd, n2, ic_const, grads, exp_avg,
+                                exp_avg_sq, mask, step_ptr, step0, k, loss_history, k_steps, workspace, workspace_bytes, ctrl, ctrl_bytes,
+                                stream, lr_steps);
 }
 
 static int optim_launch(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, const uint8_t* mask, int64_t n,

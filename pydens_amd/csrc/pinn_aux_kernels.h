@@ -63,13 +63,15 @@ struct PinnOptK {
 
 // m / v: the two state arrays (exp_avg | momentum_buffer | grad_avg, exp_avg_sq | square_avg); `first`: step 1 of the optimizer (SGD: no
 // momentum buffer yet). A rule writes only the state it owns.
+// lr / decay: the learning rate of THIS step (SGD, RMSprop) and AdamW's 1 - lr * weight_decay; o.lr / o.decay for a constant rate, the
+// iteration's entries of the control block under a schedule (PinnFitCtrl::lr / ::decay). Adam's and AdamW's rate rides in step_size.
 PINN_DEVICE void pinn_optim_apply(const PinnOptK& o, float* params, float* m, float* v, long long i, float gi, float m_old, float v_old,
-                                  float p_old, float step_size, float bc2_sqrt, bool first) {
+                                  float p_old, float lr, float decay, float step_size, float bc2_sqrt, bool first) {
     if (o.rule == PINN_OPT_ADAM && o.wd == 0.0f) {          // (plain Adam: the arithmetic the library had before the family existed)
         pinn_adam_apply(params, m, v, i, gi, m_old, v_old, p_old, step_size, bc2_sqrt, o.b1, o.b2, o.eps);
         return;
     }
-    if (o.rule == PINN_OPT_ADAMW) p_old *= o.decay;                         // param.mul_(1 - lr * weight_decay)
+    if (o.rule == PINN_OPT_ADAMW) p_old *= decay;                         // param.mul_(1 - lr * weight_decay)
     else if (o.wd != 0.0f) gi = fmaf(o.wd, p_old, gi);                      // grad = grad.add(param, alpha=weight_decay)
     if (o.rule == PINN_OPT_ADAM || o.rule == PINN_OPT_ADAMW) {
         pinn_adam_apply(params, m, v, i, gi, m_old, v_old, p_old, step_size, bc2_sqrt, o.b1, o.b2, o.eps);
@@ -80,7 +82,7 @@ PINN_DEVICE void pinn_optim_apply(const PinnOptK& o, float* params, float* m, fl
             m[i] = buf;
             gi = o.nesterov ? fmaf(o.momentum, buf, gi) : buf;              // grad.add(buf, alpha=momentum)
         }
-        params[i] = p_old - o.lr * gi;                                      // param.add_(grad, alpha=-lr)
+        params[i] = p_old - lr * gi;                                        // param.add_(grad, alpha=-lr)
     } else {                                                                // PINN_OPT_RMSPROP
         const float sq = fmaf(o.one_m_alpha, gi * gi, o.alpha * v_old);     // square_avg.mul_(alpha).addcmul_(grad, grad, value=1 - alpha)
         v[i] = sq;
@@ -96,16 +98,16 @@ PINN_DEVICE void pinn_optim_apply(const PinnOptK& o, float* params, float* m, fl
         if (o.momentum > 0.0f) {
             const float buf = fmaf(o.momentum, m_old, gi / avg);            // buf.mul_(momentum).addcdiv_(grad, avg)
             m[i] = buf;
-            params[i] = p_old - o.lr * buf;
+            params[i] = p_old - lr * buf;
         } else {
-            params[i] = p_old - o.lr * (gi / avg);                          // param.addcdiv_(grad, avg, value=-lr)
+            params[i] = p_old - lr * (gi / avg);                            // param.addcdiv_(grad, avg, value=-lr)
         }
     }
 }
 
-PINN_DEVICE void pinn_optim_update(const PinnOptK& o, float* params, float gi, float* m, float* v, long long i, float step_size,
-                                   float bc2_sqrt, bool first) {
-    pinn_optim_apply(o, params, m, v, i, gi, m[i], v[i], params[i], step_size, bc2_sqrt, first);
+PINN_DEVICE void pinn_optim_update(const PinnOptK& o, float* params, float gi, float* m, float* v, long long i, float lr, float decay,
+                                   float step_size, float bc2_sqrt, bool first) {
+    pinn_optim_apply(o, params, m, v, i, gi, m[i], v[i], params[i], lr, decay, step_size, bc2_sqrt, first);
 }
 
 // ------------------------------------------------------------------------------------------------------------
@@ -186,13 +188,20 @@ struct PinnFitCtrl {
                                         // block, not baked into the graph's nodes, a recorded chunk survives across fit calls)
     float step_size[PINN_FIT_CHUNK_MAX], bc2_sqrt[PINN_FIT_CHUNK_MAX];      // pinn_adam_scalars per iteration (computed on the host in
                                                                              // double, as for the eager loop: bit-identical updates)
+    // the learning rate of every iteration (pinn_fit_steps_optim_sched; a constant rate fills both arrays with one value): lr[k] is what
+    // SGD and RMSprop multiply with, decay[k] AdamW's 1 - lr_k * weight_decay formed on the host like PinnOptK::decay; Adam's and AdamW's
+    // rate is in step_size[k]. A recorded chunk reads all of them here, so it replays under any rate.
+    float lr[PINN_FIT_CHUNK_MAX], decay[PINN_FIT_CHUNK_MAX];
 };
 struct PinnFitCtrlArgs { PinnFitCtrl c; };
+// (the block travels to pinn_fit_ctrl_kernel BY VALUE, next to the destination pointer: kernel arguments end at 4 KB)
+static_assert(sizeof(PinnFitCtrlArgs) + sizeof(PinnFitCtrl*) <= 4096, "the control block no longer fits the kernel arguments of ONE launch");
 PINN_AUX_GLOBAL void PINN_LAUNCH_BOUNDS(128) pinn_fit_ctrl_kernel(PinnFitCtrl* dst, PinnFitCtrlArgs a) {
     const int t = PINN_TID;
     if (t == 0) { dst->call_index0 = a.c.call_index0; dst->loss_base = a.c.loss_base; dst->step0 = a.c.step0; dst->pad = 0;
                   dst->k0 = a.c.k0; dst->k1 = a.c.k1; }
-    if (t < PINN_FIT_CHUNK_MAX) { dst->step_size[t] = a.c.step_size[t]; dst->bc2_sqrt[t] = a.c.bc2_sqrt[t]; }
+    if (t < PINN_FIT_CHUNK_MAX) { dst->step_size[t] = a.c.step_size[t]; dst->bc2_sqrt[t] = a.c.bc2_sqrt[t];
+                                  dst->lr[t] = a.c.lr[t]; dst->decay[t] = a.c.decay[t]; }
 }
 
 // ------------------------------------------------------------------------------------------------------------
@@ -229,11 +238,14 @@ PINN_DEVICE void pinn_reduce_body(const PinnReduceArgs& A) {
     const int n_wg = A.n_wg, p_core = A.p_core;
     int step_value = A.step_value;
     float step_size = A.step_size, bc2_sqrt = A.bc2_sqrt;
+    float lr = A.opt.lr, decay = A.opt.decay;
     float* loss_out = A.loss_out;
-    if (A.ctrl) {           // (graph replay: this iteration's Adam step and loss slot come from the control block)
+    if (A.ctrl) {           // (graph replay: this iteration's Adam step, learning rate and loss slot come from the control block)
         step_value = A.ctrl->step0 + A.ctrl_k;
         step_size = A.ctrl->step_size[A.ctrl_k];
         bc2_sqrt = A.ctrl->bc2_sqrt[A.ctrl_k];
+        lr = A.ctrl->lr[A.ctrl_k];
+        decay = A.ctrl->decay[A.ctrl_k];
         loss_out = A.ctrl->loss_base + A.ctrl_k;
     }
     const int pl = tid % LC, ch = tid / LC;
@@ -293,7 +305,7 @@ PINN_DEVICE void pinn_reduce_body(const PinnReduceArgs& A) {
         const float t = (float)t64;
         A.grads[p] = t;
         if (loss_out && p == A.off_loss) loss_out[0] = t;
-        if (upd) pinn_optim_apply(A.opt, A.params, A.m, A.v, p, t, m_old, v_old, p_old, step_size, bc2_sqrt, step_value == 1);
+        if (upd) pinn_optim_apply(A.opt, A.params, A.m, A.v, p, t, m_old, v_old, p_old, lr, decay, step_size, bc2_sqrt, step_value == 1);
     }
     if (A.do_adam && PINN_BID == 0 && tid == 0) A.step_ptr[0] = step_value;
     // fit chunks: this iteration's tile kernel is through with the batch buffer -- the batch of the next iteration is drawn here
@@ -384,7 +396,7 @@ pinn_optim_kernel(float* params, const float* grads, float* m, float* v, const u
         step_value = step_ptr[0];
         if (opt.rule == PINN_OPT_ADAM || opt.rule == PINN_OPT_ADAMW) pinn_adam_scalars((double)step_value, opt.lr, opt.b1, opt.b2, &step_size, &bc2_sqrt);
     }
-    pinn_optim_update(opt, params, grads[i], m, v, i, step_size, bc2_sqrt, step_value == 1);
+    pinn_optim_update(opt, params, grads[i], m, v, i, opt.lr, opt.decay, step_size, bc2_sqrt, step_value == 1);
 }
 
 // one thread per point. Counter = (point low, point high, call low, call high | block << 28): block b < 8 supplies the

@@ -143,6 +143,7 @@ pinn_fit_kernel(const PinnKArgs A0, const PinnFitP P) {
     const int step0 = ctrl->step0;
     for (int k = 0; k < P.k_steps; ++k) {
         const float step_size = ctrl->step_size[k], bc2_sqrt = ctrl->bc2_sqrt[k];     // (fetched here: the loads ride behind the tile pass)
+        const float lr_k = ctrl->lr[k], decay_k = ctrl->decay[k];                     // (this iteration's learning rate: the block's, never opt's)
         const bool first = step0 + k == 1;                                            // (SGD: no momentum buffer yet)
         // (a) the batch of iteration k, the points of this (virtual) workgroup's tiles only (the tile body reads nothing else). The
         //     one-CU form draws the batch of iteration k + 1 at the end of (d) instead -- the tile pass is through with the buffer by
@@ -211,7 +212,7 @@ pinn_fit_kernel(const PinnKArgs A0, const PinnFitP P) {
                     if (k + 1 == P.k_steps) P.grads[p] = t[q];
                     if (p == P.off_loss) ctrl->loss_base[k] = t[q];
                 }
-                if (mask_reg ? upd[q] : (!P.mask || P.mask[p])) pinn_optim_update(opt, my, t[q], my + sst, my + 2 * sst, p, step_size, bc2_sqrt, first);
+                if (mask_reg ? upd[q] : (!P.mask || P.mask[p])) pinn_optim_update(opt, my, t[q], my + sst, my + 2 * sst, p, lr_k, decay_k, step_size, bc2_sqrt, first);
             }
         }
         if (RES && k + 1 < P.k_steps) draw(k + 1);

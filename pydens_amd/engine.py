@@ -159,7 +159,10 @@ def bind(lib):
                                          ctypes.c_uint64, ctypes.c_uint64, ip, i32, i32, f32, vp, vp, vp, vp, vp, i32, op,
                                          vp, i32, vp, ctypes.c_size_t, vp]
     lib.pinn_fit_steps_optim_graph.argtypes = lib.pinn_fit_steps_optim.argtypes[:-1] + [vp, ctypes.c_size_t, vp]
-    for name in ('pinn_optim_step', 'pinn_optim_step_at', 'pinn_residual_optim_step', 'pinn_fit_steps_optim', 'pinn_fit_steps_optim_graph'):
+    # ... and the launch-graph form under a learning-rate schedule: one more argument, the k_steps rates in host memory
+    lib.pinn_fit_steps_optim_sched.argtypes = lib.pinn_fit_steps_optim_graph.argtypes + [ctypes.POINTER(f32)]
+    for name in ('pinn_optim_step', 'pinn_optim_step_at', 'pinn_residual_optim_step', 'pinn_fit_steps_optim', 'pinn_fit_steps_optim_graph',
+                 'pinn_fit_steps_optim_sched'):
         getattr(lib, name).restype = i32
     lib.pinn_set_tanh_mode.argtypes = [vp, i32]
     lib.pinn_set_tanh_mode.restype = i32
@@ -214,7 +217,7 @@ ABI_SYMBOLS = ('pinn_create', 'pinn_create_ex', 'pinn_destroy', 'pinn_layout', '
                'pinn_last_tile_ms', 'pinn_last_wgrad_ms', 'pinn_last_kernel_name', 'pinn_last_wgrad_kernel_name', 'pinn_debug_last_kernel',
                'pinn_debug_prepass_in_kernel', 'pinn_debug_wgx_chunk_bytes', 'pinn_debug_max_wgs_per_cu', 'pinn_debug_fit_persistent', 'pinn_fit_chunk_status', 'pinn_set_act_params', 'pinn_debug_fit_onecu_rounds', 'pinn_debug_fit_graph_stats', 'pinn_last_launch_info',
                'pinn_optim_step', 'pinn_optim_step_at', 'pinn_residual_optim_step', 'pinn_fit_steps_optim', 'pinn_fit_steps_optim_graph',
-               'pinn_reduce_rows', 'pinn_last_reduce_kernel_name', 'pinn_port_probe',
+               'pinn_fit_steps_optim_sched', 'pinn_reduce_rows', 'pinn_last_reduce_kernel_name', 'pinn_port_probe',
                'pinn_lbfgs_ctrl_bytes', 'pinn_lbfgs_workspace_bytes', 'pinn_lbfgs_direction',
                'pinn_resample_workspace_bytes', 'pinn_resample_points', 'pinn_resample_redraw',
                'pinn_last_error', 'pinn_backend')
@@ -478,10 +481,11 @@ class Net:
 
     def fit_steps(self, residual, params, xs, columns, seed, call_index0, grads, workspace, exp_avg, exp_avg_sq, mask,
                   step_tensor, step0, lr, betas, eps, loss_history, k_steps, dir_cols=(), n2=0, ic_const=0.0, stream=None, ctrl=None,
-                  optim=None):
+                  optim=None, lr_steps=None):
         """ `k_steps` iterations of the fit loop (sample -> fused step -> Adam) enqueued by one call (include/pinn.h
         pinn_fit_steps); `xs` is the [N, d] batch buffer every iteration overwrites, `loss_history` a float32 device tensor
-        with at least k_steps entries. """
+        with at least k_steps entries. `lr_steps`: the learning rate of each of the k_steps iterations (a schedule; include/pinn.h
+        pinn_fit_steps_optim_sched) -- with or without `ctrl`, with `optim` or plain Adam's (betas, eps); `lr` is then not used. """
         for t, name in ((params, 'params'), (xs, 'xs'), (grads, 'grads'), (exp_avg, 'exp_avg'), (exp_avg_sq, 'exp_avg_sq'),
                         (loss_history, 'loss_history')):
             _check(t, name)
@@ -495,13 +499,23 @@ class Net:
         b = (ctypes.c_float * d)(*[float(c[2]) for c in columns])
         dirs, nd = self._dirs(dir_cols)
         # (`optim`: the update rule of pinn_fit_steps_optim / _optim_graph instead of plain Adam's lr, betas, eps)
+        rates = None
+        if lr_steps is not None:
+            if len(lr_steps) != k_steps:
+                raise ValueError(f'lr_steps must hold {k_steps} rates, one per iteration')
+            rates = (ctypes.c_float * max(1, k_steps))(*[float(v) for v in lr_steps])
+            if optim is None:       # (plain Adam as a rule of the family: the same arithmetic, include/pinn.h pinn_optim_t)
+                optim = Optim.build(OPT_ADAM, lr, betas=betas, eps=eps)
         rule = (float(lr), float(betas[0]), float(betas[1]), float(eps)) if optim is None else (ctypes.byref(optim), )
         common = (self.handle, ctypes.byref(residual), _ptr(params), _ptr(xs), xs.shape[0], kind, a, b,
                   int(seed) & (2 ** 64 - 1), int(call_index0), dirs, nd, n2, float(ic_const), _ptr(grads), _ptr(exp_avg),
                   _ptr(exp_avg_sq), _ptr(mask), _ptr(step_tensor), int(step0), *rule,
                   _ptr(loss_history), int(k_steps), _ptr(workspace), workspace.numel() * workspace.element_size())
         with _on_device(params):
-            if optim is not None:
+            if rates is not None:
+                self._raise(self.lib.pinn_fit_steps_optim_sched(*common, _ptr(ctrl), 0 if ctrl is None else ctrl.numel() * ctrl.element_size(),
+                                                                _stream(xs) if stream is None else stream, rates))
+            elif optim is not None:
                 if ctrl is not None:
                     self._raise(self.lib.pinn_fit_steps_optim_graph(*common, _ptr(ctrl), ctrl.numel() * ctrl.element_size(),
                                                                     _stream(xs) if stream is None else stream))

@@ -146,6 +146,25 @@ class FlatOptimizer:
     def steps_of(self, off):
         return sum(n for n, skipped in self._served() if off not in skipped)
 
+    def set_lr(self, lr):
+        """ the learning rate of the coming step(s) (a schedule, Solver.fit(lr_scheduler=...)): every eager call hands it to the library by
+        value, through `lr` (plain Adam, L-BFGS) or the `Optim` struct """
+        self.lr = float(lr)
+        if self.optim is not None:
+            self.optim.lr = self.lr
+
+    def shadow(self):
+        """ the one-parameter host optimizer a learning-rate scheduler is built over: it carries `param_groups[0]['lr']` (and the momentum /
+        betas a scheduler may look for) and never steps anything -- torch's own scheduler code computes every rate on it """
+        if getattr(self, '_shadow', None) is None:
+            weight = [torch.zeros(1, requires_grad=True)]
+            hyper = self.hyper_parameters
+            if 'betas' in hyper:
+                self._shadow = torch.optim.Adam(weight, lr=self.lr, betas=tuple(hyper['betas']))
+            else:
+                self._shadow = torch.optim.SGD(weight, lr=self.lr, momentum=float(hyper.get('momentum', 0.0)))
+        return self._shadow
+
     def step(self, grads, loss_out=None, stream=None):
         """ loss_out: device address that receives grads[off_loss] in the same launch (the fit's loss history) """
         self.t += 1
@@ -258,8 +277,8 @@ class FlatLBFGS(FlatOptimizer):
     def _direction(self, grads, mode, apply, stream):
         hp = self.hyper_parameters
         self.model.net.lbfgs_direction(self.model.flat, grads, self.prev_grad, self.d, self.S, self.Y, self.mask, hp['history_size'], mode,
-                                       apply, self.step_length, hp['lr'], hp['tolerance_grad'], hp['tolerance_change'], self.ctrl, self.rows,
-                                       stream=stream)
+                                       apply, self.step_length, self.lr, hp['tolerance_grad'], hp['tolerance_change'], self.ctrl, self.rows,
+                                       stream=stream)           # (self.lr: hp['lr'], or this iteration's rate of a schedule -- set_lr)
         self.last = dict(zip(engine.LBFGS_CTRL, self.ctrl[:len(engine.LBFGS_CTRL)].tolist()))       # the ONE read-back per evaluation
         return self.last
 
@@ -424,6 +443,9 @@ class Solver:
         if os.environ.get('PYDENS_AMD_CRITERION'):
             self.set_criterion_path(os.environ['PYDENS_AMD_CRITERION'])
         self.optimizer = None
+        self.lr_scheduler = None            # fit(lr_scheduler=...): the live torch.optim.lr_scheduler object
+        self.lrs = []                       # the learning rate of every iteration stepped so far (host values; aligned with `losses`)
+        self._lr_queue = []                 # rates drawn ahead of the device, one chunk at a time; the head is the next step's
         self.optimizer_path = 'torch'       # set_optimizer_path: optimizers other than plain Adam as torch.optim code or on the fused kernels
         self.last_fit_optimizer = None
         self.optimizer_refusal = None       # why the last `fit(optimizer='LBFGS')` under the 'fused' path kept torch.optim (None: it did not)
@@ -1209,11 +1231,143 @@ class Solver:
     def fit(self, niters, batch_size, sampler=None, loss_terms='equation', optimizer='Adam',
             criterion=nn.MSELoss(), lr=0.005, **kwargs):
         """ reference model_torch.py:364-464. Under torch.distributed `batch_size` stays the GLOBAL number of points per
-        iteration (the reference's meaning); rank r steps on its share of it. """
+        iteration (the reference's meaning); rank r steps on its share of it.
+        `lr_scheduler`: the name of a class in torch.optim.lr_scheduler (built with `lr_scheduler_kwargs`) or a callable
+        `factory(optimizer) -> scheduler`; the torch loop `opt.step(); sched.step()` once per iteration, on every step path
+        (`_set_scheduler`). `fit(optimizer=None)` carries the running schedule on; a new optimizer without one has a constant rate. """
+        lr_scheduler, lr_scheduler_kwargs = kwargs.pop('lr_scheduler', None), kwargs.pop('lr_scheduler_kwargs', None)
         with self._device_guard():
-            return self._fit(niters, batch_size, sampler, loss_terms, optimizer, criterion, lr, **kwargs)
+            return self._fit(niters, batch_size, sampler, loss_terms, optimizer, criterion, lr, lr_scheduler, lr_scheduler_kwargs, **kwargs)
 
-    def _fit(self, niters, batch_size, sampler, loss_terms, optimizer, criterion, lr, **kwargs):
+    # ---- learning-rate schedules -------------------------------------------------------------------------------------------------
+    def _scheduled_optimizer(self):
+        """ the torch optimizer a scheduler is built over: the real one (TorchOptimizerAdapter) or the flat optimizer's host shadow """
+        opt = self.optimizer
+        return opt.opt if isinstance(opt, TorchOptimizerAdapter) else opt.shadow()
+
+    def _set_scheduler(self, spec, kwargs, fresh):
+        """ `fit(lr_scheduler=spec, lr_scheduler_kwargs=kwargs)`. Semantics: torch's `opt.step(); sched.step()` per iteration; the rate of
+        iteration k is what `param_groups[0]['lr']` reads in front of step k. The rates are torch's own: its scheduler code runs on the host,
+        over the real optimizer on the torch path, over a one-parameter shadow optimizer for the flat optimizers -- there they are drawn a chunk
+        ahead into a queue and travel to the kernels per iteration (include/pinn.h pinn_fit_steps_optim_sched). fresh: a new optimizer. """
+        if spec is None:
+            if fresh:
+                self.lr_scheduler, self._lr_queue = None, []
+            return
+        target = self._scheduled_optimizer()
+        if self._lr_queue:
+            # (rates drawn ahead that no step used: the optimizer's rate is that of its NEXT step again before torch's rules look at it)
+            target.param_groups[0]['lr'] = self._lr_queue[0]
+        before = [(g['lr'], g.get('initial_lr')) for g in target.param_groups]
+        cycled = [(g.get('momentum'), g.get('betas')) for g in target.param_groups]
+        previous = (self.lr_scheduler, list(self._lr_queue))
+        self.lr_scheduler, self._lr_queue = None, []
+
+        def restore():
+            # (the optimizer stays as it was: usable by a later fit(optimizer=None), at its own rate)
+            del target.param_groups[len(before):]
+            for g, (rate, initial) in zip(target.param_groups, before):
+                g['lr'] = rate
+                if initial is None:
+                    g.pop('initial_lr', None)
+                else:
+                    g['initial_lr'] = initial
+            for g, (momentum, betas) in zip(target.param_groups, cycled):
+                if momentum is not None:
+                    g['momentum'] = momentum
+                if betas is not None:
+                    g['betas'] = betas
+            self.lr_scheduler, self._lr_queue = (None, []) if fresh else previous
+
+        def refuse(error, message):
+            restore()
+            raise error(message)
+        if isinstance(spec, str):
+            cls = getattr(torch.optim.lr_scheduler, spec, None)
+            if not (isinstance(cls, type) and (issubclass(cls, torch.optim.lr_scheduler.LRScheduler) or spec == 'ReduceLROnPlateau')):
+                refuse(ValueError, f'lr_scheduler={spec!r}: torch.optim.lr_scheduler has no scheduler class of that name')
+            build = lambda opt: cls(opt, **(kwargs or {}))
+        elif callable(spec):
+            if kwargs:
+                refuse(ValueError, 'lr_scheduler_kwargs go with the NAME of a scheduler class; a factory builds its scheduler itself')
+            build = spec
+        else:
+            refuse(ValueError, f'lr_scheduler must be the name of a class in torch.optim.lr_scheduler or a callable, got {spec!r}')
+        try:
+            sched = build(target)
+        except Exception:           # (torch's own argument checks raise here as they do in the torch loop)
+            restore()
+            raise
+        import inspect
+        needs = [p.name for p in inspect.signature(sched.step).parameters.values()
+                 if p.default is inspect.Parameter.empty and p.kind in (p.POSITIONAL_ONLY, p.POSITIONAL_OR_KEYWORD)]
+        if needs:
+            refuse(NotImplementedError, f'lr_scheduler {type(sched).__name__}: its step() needs {needs} -- a metric-driven schedule would read '
+                                        'the loss back to the host every iteration, which Solver.fit never does; out of scope')
+        self.lr_scheduler = sched
+        message = self._rate_refusal()
+        if message is not None:
+            refuse(NotImplementedError, message)
+        if not isinstance(self.optimizer, TorchOptimizerAdapter):
+            if [(g.get('momentum'), g.get('betas')) for g in target.param_groups] != cycled:
+                refuse(NotImplementedError, f'lr_scheduler {type(sched).__name__} also schedules momentum / betas, which the HIP optimizer '
+                                            'kernels take as constants of a fit; pass cycle_momentum=False')
+            target.step()       # (nothing to step: torch's order check then sees opt.step() in front of the first sched.step())
+
+    def _rate_refusal(self):
+        """ why the scheduler's current rate cannot be stepped with, in words (None: it can) """
+        groups = self.lr_scheduler.optimizer.param_groups
+        if len(groups) != 1:
+            return f'lr_scheduler {type(self.lr_scheduler).__name__} leaves {len(groups)} param groups; the kernels step ONE flat buffer at one rate'
+        rate = groups[0]['lr']
+        if not isinstance(rate, (int, float)) or not math.isfinite(rate) or rate < 0:
+            return f'lr_scheduler {type(self.lr_scheduler).__name__} gives the learning rate {rate!r}; a rate must be a finite number >= 0'
+        return None
+
+    def _draw_rates(self, k):
+        """ the rates of the next k steps of a flat optimizer, in `_lr_queue`: read, then `sched.step()`, as often as needed """
+        sched = self.lr_scheduler
+        while len(self._lr_queue) < k:
+            message = self._rate_refusal()
+            if message is not None:
+                raise NotImplementedError(message)
+            self._lr_queue.append(float(sched.optimizer.param_groups[0]['lr']))
+            sched.step()
+        return self._lr_queue[:k]
+
+    def _rate_begin(self):
+        """ in front of ONE step of the per-iteration paths: the step's rate, handed to the optimizer (None: no schedule) """
+        if self.lr_scheduler is None:
+            return None
+        opt = self.optimizer
+        if isinstance(opt, TorchOptimizerAdapter):
+            if self.lr_scheduler.optimizer is opt.opt:
+                return float(opt.opt.param_groups[0]['lr'])
+            # (TorchOptimizerAdapter.continuing took over from a flat optimizer in the middle of its schedule: the shadow goes on carrying it)
+            rate = self._draw_rates(1)[0]
+            for group in opt.opt.param_groups:
+                group['lr'] = rate
+            return rate
+        rate = self._draw_rates(1)[0]
+        opt.set_lr(rate)
+        return rate
+
+    def _rate_end(self, rate):
+        """ behind that step: the schedule moves on, the rate is on record """
+        if rate is None:
+            opt = self.optimizer
+            self.lrs.append(float(opt.opt.param_groups[0]['lr'] if isinstance(opt, TorchOptimizerAdapter) else opt.lr))
+            return
+        if self._lr_queue:
+            self._lr_queue.pop(0)
+        else:
+            self.lr_scheduler.step()
+            message = self._rate_refusal()
+            if message is not None:
+                raise NotImplementedError(message)
+        self.lrs.append(rate)
+
+    def _fit(self, niters, batch_size, sampler, loss_terms, optimizer, criterion, lr, lr_scheduler=None, lr_scheduler_kwargs=None, **kwargs):
         model = self.model
         for num in self._constraints_seen:          # variables an earlier fit call brought to life are trainable now
             model.dormant_variables -= self._born_in_constraint.get(num, set())
@@ -1230,6 +1384,7 @@ class Solver:
                 self.optimizer = TorchOptimizerAdapter(model, optimizer, lr, **kwargs)
         elif self.optimizer is None:
             raise ValueError('optimizer=None reuses the optimizer of a previous fit call; there is none yet')
+        self._set_scheduler(lr_scheduler, lr_scheduler_kwargs, fresh=optimizer is not None)
         self._generic_graph = None          # launch graphs of the generic step are recorded per fit call (closure constants may have changed)
         model.train()
         loss_terms = loss_terms if isinstance(loss_terms, (tuple, list)) else (loss_terms, )
@@ -1302,6 +1457,7 @@ class Solver:
         by_closure = self.optimizer.needs_closure
         for it in tqdm(range(niters), disable=None):
             xs = self._sample(local_batch, sampler, stream)
+            rate = self._rate_begin()               # (a schedule: this iteration's learning rate, by value through the calls below)
             if by_closure:
                 # the batch is drawn ONCE; every closure call re-runs the gradient part of the iteration on it, and the iteration's loss is
                 # what `step(closure)` returns: the loss at its first evaluation (`loss = opt.step(closure)`)
@@ -1315,11 +1471,13 @@ class Solver:
                 loss = self.optimizer.step(self.grads, stream=stream, closure=closure)
                 history[it:it + 1].copy_(loss.reshape(1))
                 done[0] = it + 1
+                self._rate_end(rate)
                 continue
             if one_launch:
                 # Adam rides in the gradient-reduction launch, which also drops the loss into history[it]
                 self._fused_step(xs, 1, adam=self.optimizer, loss_out=history_ptr + 4 * it, stream=stream)
                 done[0] = it + 1
+                self._rate_end(rate)
                 continue
             if fused:
                 # (two to four launches per iteration: replaying them as a launch graph measured 0.048 -> 0.046 ms/it at batch 500 and
@@ -1335,6 +1493,7 @@ class Solver:
                 self.optimizer.step(self.grads)
                 history[it:it + 1].copy_(self.grads[lay.off_loss:lay.off_loss + 1])
             done[0] = it + 1
+            self._rate_end(rate)
 
     FIT_CHUNK = 128             # iterations per pinn_fit_steps call (progress bar / KeyboardInterrupt granularity)
     FIT_CTRL_ON_HOST = False    # (tests on the CPU emulator: the control block of pinn_fit_steps_graph in host memory)
@@ -1383,11 +1542,13 @@ class Solver:
                 else:
                     seed, call0 = self._sample_seed, self._sample_calls
                 t0, applied = adam.t, k
+                # (a schedule: the chunk's rates, drawn ahead; how many of them leave the queue is decided by `applied` below)
+                rates = self._draw_rates(k) if self.lr_scheduler is not None else None
                 try:
                     model.net.fit_steps(self.program, model.flat, xs, columns, seed, call0, self.grads, ws, adam.exp_avg,
                                         adam.exp_avg_sq, adam.mask, adam.step_count, adam.t + 1, adam.lr, adam.betas, adam.eps,
                                         history[it:it + k], k, dir_cols=spec.dir_cols, n2=n2, ic_const=model.kernel_ic_const(),
-                                        stream=stream, ctrl=ctrl, optim=adam.optim)
+                                        stream=stream, ctrl=ctrl, optim=adam.optim, lr_steps=rates)
                     if os.environ.get('PYDENS_AMD_FIT_PERSIST') == '1' and model.net.lib.pinn_fit_chunk_status() != 0:
                         # the opt-in GRID form of the one-launch chunk gave up at its device-wide wait: nothing of the chunk was applied
                         # (include/pinn.h pinn_fit_chunk_status; the check synchronises with the device once per chunk)
@@ -1400,6 +1561,11 @@ class Solver:
                     raise
                 finally:
                     adam.t = t0 + applied
+                    if rates is None:
+                        self.lrs.extend([float(adam.lr)] * applied)
+                    else:
+                        self.lrs.extend(rates[:applied])
+                        del self._lr_queue[:applied]
                     if own is not None:
                         sampler.next_device_call(applied)
                     else:
