@@ -27,6 +27,19 @@ int fail(const char* fmt, ...) {
 
 int round16(int v) { return (v + 15) / 16 * 16; }
 
+// one launch of a small kernel of this file on either backend; a refused launch is the error "<what> launch failed"
+template <typename... K, typename... A>
+int launch(const char* what, void (*kernel)(K...), int grid, int threads, size_t smem, void* stream, const A&... args) {
+#ifdef PINN_EMU
+    (void)what; (void)stream;
+    emu::launch(grid, threads, smem, [&] { kernel(args...); });
+#else
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(threads), smem, (hipStream_t)stream, args...);
+    if (hipGetLastError() != hipSuccess) return fail("%s launch failed", what);
+#endif
+    return 0;
+}
+
 int g_profile = 0;
 long long* g_phase_prof = nullptr;
 #ifndef PINN_EMU
@@ -62,16 +75,6 @@ PINN_HIDDEN char g_pinn_last_kernel_name[96] = "";
 PINN_HIDDEN char g_pinn_last_wgrad_name[96] = "";
 PINN_HIDDEN int g_pinn_last_launch[4] = {0, 0, 0, 0};   // grid, workgroups per CU of the plan, threads, dynamic LDS bytes
 namespace {
-// set while pinn_fit_steps_graph captures a chunk: the sample and reduce launches then read their per-iteration values from the device
-// control block (PinnFitCtrl) at index `k` instead of taking them by value
-struct FitCapture { const PinnFitCtrl* ctrl; int k; };
-thread_local FitCapture g_fit_capture = {nullptr, 0};
-// set by pinn_fit_steps around the step of iteration k < K - 1: its reduction launch also draws the batch of iteration k + 1
-thread_local PinnNextBatch g_fit_next = {nullptr, 0, {}, 0u, 0u, 0ull};
-// set by pinn_fit_steps_graph around ONE residual step call: run_train then launches the one-launch fit chunk (pinn_fit_kernel) over the
-// tiles of that step instead of tile kernel + reduction; `done` says whether it did (0: the plan does not qualify -- nothing was launched)
-struct FitPersist { PinnFitP p; int active, done; };
-thread_local FitPersist g_fit_persist = {{}, 0, 0};
 int g_pinn_debug_flags = 0;         // -DPINN_DEBUG_ABI builds: pinn_debug_set_flags
 }
 
@@ -329,12 +332,40 @@ int check_dirs(const pinn_net* net, const int* dir_cols, int nd, int n2p) {
     return 0;
 }
 
-// the update that rides in a step's last reduction launch (or in the one-launch fit chunk): buffers, step, rule
-struct AdamArgs {
+// a request for the one-launch fit chunk (pinn_fit_kernel.h) in place of tile kernel + reduction. The caller fills ctrl, k_steps, xs, n and
+// spec of `p`; run_train fills the rest and says in `launched` whether the chunk went out (false: the plan does not qualify, NOTHING was
+// launched)
+struct OneLaunch { PinnFitP p; bool launched; };
+
+// what rides behind the tile pass of a step, handed down from residual_optim_step through residual_step_impl and run_train to
+// launch_reduce: the update in the last reduction launch (buffers, step, rule) and the context of a fit chunk around it
+struct StepTail {
     float* params; float* m; float* v; const unsigned char* mask; int* step_ptr;
     int step_value; PinnOptK opt;
     float* loss_out; int off_loss;
+    PinnNextBatch next;             // the batch of the NEXT iteration, drawn by the same launch (n == 0: none)
+    const PinnFitCtrl* capture;     // a chunk is being captured: the launches read their per-iteration values from this control block at
+    int capture_k;                  // index capture_k (nullptr: they take them by value)
+    OneLaunch* persist;             // nullptr: no such request
 };
+
+// the arguments of one step call and of one fit chunk, filled once by the exported entry point and handed on by reference
+struct StepCall {
+    pinn_t* net; const pinn_residual_t* residual; const float* params; const float* xs; int64_t n_points; const int* dir_cols; int nd, n2;
+    const float* ic_streams; float ic_const; float* grads; void* workspace; size_t workspace_bytes; void* stream;
+};
+struct OptimState { float* params; float* exp_avg; float* exp_avg_sq; const uint8_t* mask; int32_t* step_ptr; };
+struct FitCall {
+    StepCall step;                  // (step.xs is `xs` below, the batch buffer every iteration overwrites; no ic_streams in a fit chunk)
+    float* xs; const int* kind; const float* a; const float* b; uint64_t seed, call_index0;
+    OptimState state; int32_t step0; PinnOptK opt;
+    float* loss_history; int32_t k_steps; void* ctrl; size_t ctrl_bytes; const float* lr_steps;
+};
+
+// the tail of a step that only updates: no next batch, no capture, no one-launch request (off_loss: the caller's)
+StepTail update_tail(const OptimState& s, int32_t step, const PinnOptK& opt, float* loss_out, int off_loss = -1) {
+    return {s.params, s.exp_avg, s.exp_avg_sq, s.mask, s.step_ptr, step, opt, loss_out, off_loss, {nullptr, 0, {}, 0u, 0u, 0ull}, nullptr, 0, nullptr};
+}
 
 // the decimal a float was most likely written as, as a double: the shortest one that rounds back to it. torch derives 1 - alpha,
 // 1 - dampening and 1 - lr * weight_decay from the caller's Python DOUBLES; pinn_optim_t carries floats, and 1 - (double)0.99f is 1e-6
@@ -414,14 +445,13 @@ static int check_lr_steps(const float* lr_steps, int32_t k_steps) {
 
 // the control block of a chunk as pinn_fit_ctrl_kernel takes it: per iteration the bias corrections, the learning rate and what
 // derives from it -- the very numbers the eager loop hands its launches by value
-static void fit_ctrl_fill(PinnFitCtrlArgs* ca, uint64_t call_index0, float* loss_history, int32_t step0, uint64_t seed, const PinnOptK& opt,
-                          const float* lr_steps, int32_t k_steps) {
-    ca->c.call_index0 = call_index0; ca->c.loss_base = loss_history; ca->c.step0 = step0; ca->c.pad = 0;
-    ca->c.k0 = (unsigned)(seed & 0xffffffffull); ca->c.k1 = (unsigned)(seed >> 32);
+static void fit_ctrl_fill(PinnFitCtrlArgs* ca, const FitCall& f) {
+    ca->c.call_index0 = f.call_index0; ca->c.loss_base = f.loss_history; ca->c.step0 = f.step0; ca->c.pad = 0;
+    ca->c.k0 = (unsigned)(f.seed & 0xffffffffull); ca->c.k1 = (unsigned)(f.seed >> 32);
     for (int k = 0; k < PINN_FIT_CHUNK_MAX; ++k) {
-        const PinnOptK ok = (lr_steps && k < k_steps) ? optim_at_rate(opt, lr_steps[k]) : opt;
+        const PinnOptK ok = (f.lr_steps && k < f.k_steps) ? optim_at_rate(f.opt, f.lr_steps[k]) : f.opt;
         ca->c.step_size[k] = 0.0f; ca->c.bc2_sqrt[k] = 1.0f;
-        if (k < k_steps) optim_scalars(ok, (double)(step0 + k), &ca->c.step_size[k], &ca->c.bc2_sqrt[k]);
+        if (k < f.k_steps) optim_scalars(ok, (double)(f.step0 + k), &ca->c.step_size[k], &ca->c.bc2_sqrt[k]);
         ca->c.lr[k] = ok.lr; ca->c.decay[k] = ok.decay;
     }
 }
@@ -440,30 +470,41 @@ const char* g_last_reduce_name = "";
 #define PINN_REDUCE_SCALAR 0
 #endif
 int launch_reduce(const float* partials, int n_wg, int p_core, float* grads, int accumulate, void* stream,
-                  const AdamArgs* adam = nullptr) {
+                  const StepTail* tail = nullptr) {
     const bool vec = !PINN_REDUCE_SCALAR && p_core % 4 == 0 && (reinterpret_cast<uintptr_t>(partials) & 15) == 0;
     const int lc = vec ? PINN_REDUCE_LC : PINN_REDUCE_SCALAR_LC, pb = vec ? 4 * lc : lc, threads = lc * PINN_REDUCE_CH;
     const int blocks = (p_core + pb - 1) / pb;
     const size_t smem = (size_t)PINN_REDUCE_CH * pb * sizeof(double);      // (the chunk sums cross the LDS in double: [CH][PB])
-    AdamArgs z = {nullptr, nullptr, nullptr, nullptr, nullptr, 0, plain_adam(0.f, 0.f, 0.f, 0.f), nullptr, -1};
-    const AdamArgs& a = adam ? *adam : z;
-    const int do_adam = adam ? 1 : 0;
+    const StepTail z = {nullptr, nullptr, nullptr, nullptr, nullptr, 0, plain_adam(0.f, 0.f, 0.f, 0.f), nullptr, -1,
+                        {nullptr, 0, {}, 0u, 0u, 0ull}, nullptr, 0, nullptr};
+    const StepTail& a = tail ? *tail : z;
+    const int do_adam = tail ? 1 : 0;
     float step_size = 0.0f, bc2_sqrt = 1.0f;
-    if (adam) optim_scalars(a.opt, (double)a.step_value, &step_size, &bc2_sqrt);
-    PinnReduceArgs ra = {partials, n_wg, p_core, grads, accumulate, do_adam, a.params, a.m, a.v, a.mask, a.step_value, step_size, bc2_sqrt,
-                         a.opt, a.step_ptr, a.loss_out, a.off_loss, nullptr, 0,
-                         do_adam ? g_fit_next : PinnNextBatch{nullptr, 0, {}, 0u, 0u, 0ull}};
+    if (tail) optim_scalars(a.opt, (double)a.step_value, &step_size, &bc2_sqrt);
+    // (a.capture is set by the HIP build's capture_chunk alone: the emulator's reductions always take their values by value)
+    const PinnReduceArgs ra = {partials, n_wg, p_core, grads, accumulate, do_adam, a.params, a.m, a.v, a.mask, a.step_value, step_size, bc2_sqrt,
+                               a.opt, a.step_ptr, a.loss_out, a.off_loss, a.capture, a.capture_k, a.next};
     g_last_reduce_name = vec ? "pinn_reduce_kernel" : "pinn_reduce_scalar_kernel";
-#ifdef PINN_EMU
-    if (vec) emu::launch(blocks, threads, smem, [&] { pinn_reduce_kernel(ra); });
-    else emu::launch(blocks, threads, smem, [&] { pinn_reduce_scalar_kernel(ra); });
-#else
-    if (do_adam) { ra.ctrl = g_fit_capture.ctrl; ra.ctrl_k = g_fit_capture.k; }
-    if (vec) hipLaunchKernelGGL(pinn_reduce_kernel, dim3(blocks), dim3(threads), smem, (hipStream_t)stream, ra);
-    else hipLaunchKernelGGL(pinn_reduce_scalar_kernel, dim3(blocks), dim3(threads), smem, (hipStream_t)stream, ra);
-    if (hipGetLastError() != hipSuccess) return fail("reduce kernel launch failed");
-#endif
-    return 0;
+    return launch("reduce kernel", vec ? pinn_reduce_kernel : pinn_reduce_scalar_kernel, blocks, threads, smem, stream, ra);
+}
+
+// pinn_sample_points; `capture` / `capture_k` as in StepTail (the exported call: nullptr)
+int sample_points(float* xs, int64_t n_points, int d, const int* kind, const float* a, const float* b, uint64_t seed, uint64_t call_index,
+                  void* stream, const PinnFitCtrl* capture, int capture_k) {
+    if (!xs || !kind || !a || !b) return fail("null argument");
+    if (d < 1 || d > PINN_MAX_INPUTS) return fail("d=%d outside [1, %d]", d, PINN_MAX_INPUTS);
+    if (n_points <= 0) return 0;
+    PinnSampleSpec spec;
+    memset(&spec, 0, sizeof(spec));
+    spec.d = d;
+    for (int c = 0; c < d; ++c) {
+        if (kind[c] < PINN_SAMPLE_UNIFORM || kind[c] > PINN_SAMPLE_CONST) return fail("column %d: unknown sampler kind %d", c, kind[c]);
+        spec.kind[c] = kind[c]; spec.a[c] = a[c]; spec.b[c] = b[c];
+    }
+    const unsigned k0 = (unsigned)(seed & 0xffffffffull), k1 = (unsigned)(seed >> 32);
+    const unsigned c_lo = (unsigned)(call_index & 0xffffffffull), c_hi = (unsigned)(call_index >> 32);
+    return launch("sampler kernel", pinn_sample_kernel, (int)((n_points + 255) / 256), 256, 0, stream, xs, (long long)n_points, spec,
+                  k0, k1, c_lo, c_hi, capture, capture_k);
 }
 
 size_t align256(size_t v) { return (v + 255) / 256 * 256; }
@@ -485,27 +526,7 @@ const char* pinn_last_error(void) { return g_err; }
 
 int pinn_sample_points(float* xs, int64_t n_points, int d, const int* kind, const float* a, const float* b,
                        uint64_t seed, uint64_t call_index, void* stream) {
-    if (!xs || !kind || !a || !b) return fail("null argument");
-    if (d < 1 || d > PINN_MAX_INPUTS) return fail("d=%d outside [1, %d]", d, PINN_MAX_INPUTS);
-    if (n_points <= 0) return 0;
-    PinnSampleSpec spec;
-    memset(&spec, 0, sizeof(spec));
-    spec.d = d;
-    for (int c = 0; c < d; ++c) {
-        if (kind[c] < PINN_SAMPLE_UNIFORM || kind[c] > PINN_SAMPLE_CONST) return fail("column %d: unknown sampler kind %d", c, kind[c]);
-        spec.kind[c] = kind[c]; spec.a[c] = a[c]; spec.b[c] = b[c];
-    }
-    const unsigned k0 = (unsigned)(seed & 0xffffffffull), k1 = (unsigned)(seed >> 32);
-    const unsigned c_lo = (unsigned)(call_index & 0xffffffffull), c_hi = (unsigned)(call_index >> 32);
-    const int blocks = (int)((n_points + 255) / 256);
-#ifdef PINN_EMU
-    emu::launch(blocks, 256, 0, [&] { pinn_sample_kernel(xs, (long long)n_points, spec, k0, k1, c_lo, c_hi, nullptr, 0); });
-#else
-    hipLaunchKernelGGL(pinn_sample_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, xs, (long long)n_points, spec,
-                       k0, k1, c_lo, c_hi, g_fit_capture.ctrl, g_fit_capture.k);
-    if (hipGetLastError() != hipSuccess) return fail("sampler kernel launch failed");
-#endif
-    return 0;
+    return sample_points(xs, n_points, d, kind, a, b, seed, call_index, stream, nullptr, 0);
 }
 
 #ifdef PINN_DEBUG_ABI
@@ -578,6 +599,7 @@ int pinn_debug_fit_onecu_rounds(pinn_t* net, int rounds) {
 // the GRID form of the one-launch fit chunk (pinn_debug_fit_persistent 1) waits device-wide once per iteration with a bounded spin; a
 // workgroup that gives up raises a flag and the whole grid returns WITHOUT writing parameters / losses back (pinn_fit_kernel.h). The host
 // cannot see that from the launch: this call synchronises with the device and reads the flag of the last such chunk.
+// (pinn_fit_chunk_status takes no handle, so this one piece of state stays with the thread; a call's context travels in StepTail)
 static thread_local unsigned* g_fit_last_sync = nullptr;
 int pinn_fit_chunk_status(void) {
     if (!g_fit_last_sync) return 0;
@@ -855,7 +877,7 @@ int pinn_jet_forward_ws(pinn_t* net, const float* params, const float* xs, int64
 
 static int run_train(pinn_t* net, PinnKArgs* a, const Plan& plan, int nd, float* grads, int accumulate, void* workspace,
                      size_t workspace_bytes, void* stream, const pinn_program_t* pre = nullptr,
-                     const AdamArgs* adam = nullptr, const double* pre_consts64 = nullptr) {
+                     const StepTail* tail = nullptr, const double* pre_consts64 = nullptr) {
     const size_t part_bytes = align256((size_t)plan.rows() * net->lay.p_total * sizeof(float));
     const size_t slab_bytes = align256(plan.slab_bytes());
     const size_t aux_bytes = (pre && a->n_aux > 0) ? align256((size_t)a->n_aux * (size_t)a->n_points * sizeof(float)) : 0;
@@ -894,15 +916,8 @@ static int run_train(pinn_t* net, PinnKArgs* a, const Plan& plan, int nd, float*
             a->pre = *pre;          // evaluated in the prologue of the tile kernel: one launch (and one dependent-launch gap) less
             a->pre_consts64 = pc64;
             a->pre_nregs = nregs;
-        } else {
-            const int blocks = (int)((a->n_points + 255) / 256);
-#ifdef PINN_EMU
-            emu::launch(blocks, 256, 0, [&] { pinn_aux_kernel(a->xs, a->n_points, a->d, *pre, pc64, aux); });
-#else
-            hipLaunchKernelGGL(pinn_aux_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, a->xs, a->n_points, a->d,
-                               *pre, pc64, aux);
-            if (hipGetLastError() != hipSuccess) return fail("pre-pass kernel launch failed");
-#endif
+        } else if (launch("pre-pass kernel", pinn_aux_kernel, (int)((a->n_points + 255) / 256), 256, 0, stream, a->xs, a->n_points, a->d, *pre, pc64, aux)) {
+            return 1;
         }
     }
     if (plan.wt_floats_per_wg)
@@ -914,13 +929,7 @@ static int run_train(pinn_t* net, PinnKArgs* a, const Plan& plan, int nd, float*
         const int hp = net->lay.hp, blocks = (hp / 32) * (hp / 32) * net->lay.lh;
         const float* wh = a->params + net->lay.off_wh;
         const int stride = net->lay.hidden_stride;
-#ifdef PINN_EMU
-        emu::launch(blocks, 256, 32 * 33 * sizeof(float), [&] { pinn_transpose_kernel(wh, stride, hp, wt); });
-#else
-        hipLaunchKernelGGL(pinn_transpose_kernel, dim3(blocks), dim3(256), 32 * 33 * sizeof(float), (hipStream_t)stream, wh,
-                           stride, hp, wt);
-        if (hipGetLastError() != hipSuccess) return fail("transpose kernel launch failed");
-#endif
+        if (launch("transpose kernel", pinn_transpose_kernel, blocks, 256, 32 * 33 * sizeof(float), stream, wh, stride, hp, wt)) return 1;
     }
     if (wsp_bytes && net->lay.lh > 0) {
         // split-bf16 kernels: hidden weights -> hi / mid / lo bf16 MFMA fragments (the weights change every step)
@@ -930,27 +939,22 @@ static int run_train(pinn_t* net, PinnKArgs* a, const Plan& plan, int nd, float*
         const int blocks = (lh * 2 * (hp / 32) * (hp / 16) * 64 + 255) / 256;
         const float* wh = a->params + net->lay.off_wh;
         const int stride = net->lay.hidden_stride;
-#ifdef PINN_EMU
-        emu::launch(blocks, 256, 0, [&] { pinn_wsplit_kernel(wh, stride, hp, lh, wsp); });
-#else
-        hipLaunchKernelGGL(pinn_wsplit_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, wh, stride, hp, lh, wsp);
-        if (hipGetLastError() != hipSuccess) return fail("weight-split kernel launch failed");
-#endif
+        if (launch("weight-split kernel", pinn_wsplit_kernel, blocks, 256, 0, stream, wh, stride, hp, lh, wsp)) return 1;
     }
 #ifndef PINN_EMU
     ProfEvents* pe = g_profile ? prof_events() : nullptr;
     if (g_profile && !pe) return fail("hipEventCreate failed");
     if (pe) pe->have_wgrad = false;
 #endif
-    if (g_fit_persist.active) {
+    if (tail && tail->persist) {
         // a whole chunk of fit iterations in ONE launch (pinn_fit_kernel.h): the step must be one pass of a non-streamed kernel, the
         // instantiation must carry the kernel, the scratch for rows / private states must fit behind `need`. Mode 2: the one-CU form
         // (virtual workgroups, no device-scope wait) for batches of at most fit_onecu_rounds sweeps of its virtual workgroups; mode 1:
         // the grid form (every workgroup resident).
-        g_fit_persist.done = 0;
+        tail->persist->launched = false;
         long long has[3] = {0, 0, 0};
         const size_t pc = (size_t)net->lay.p_total;
-        bool ok = !plan.wgx && !plan.wt_global && !plan.split && plan.chunk_tiles >= plan.ntiles && !g_profile && adam &&
+        bool ok = !plan.wgx && !plan.wt_global && !plan.split && plan.chunk_tiles >= plan.ntiles && !g_profile &&
                   (!aux_bytes || net->prepass_in_kernel) && plan.fn(nd, plan.n2k, a, plan.grid, stream, 3, has) == 0 && has[0];
         const int vw = (int)has[1];
         const bool onecu = ok && net->fit_persistent == 2 && vw >= 2 && vw <= 8 && plan.ntiles <= (int64_t)vw * net->fit_onecu_rounds;
@@ -959,13 +963,13 @@ static int run_train(pinn_t* net, PinnKArgs* a, const Plan& plan, int nd, float*
         const size_t rows_b = align256(2 * (size_t)rows * pc * sizeof(float)), state_b = align256(3 * (size_t)states * pc * sizeof(float));
         const size_t slab1_b = onecu ? align256((size_t)vw * plan.slab_vec4_per_wg * sizeof(f32x4)) : 0;      // the virtual workgroups' own slabs
         if ((onecu || gridform) && workspace_bytes >= need + rows_b + state_b + 256 + slab1_b) {
-            PinnFitP& P = g_fit_persist.p;
+            PinnFitP& P = tail->persist->p;
             P.rows = reinterpret_cast<float*>(ws + need);
             P.state = reinterpret_cast<float*>(ws + need + rows_b);
             P.sync = reinterpret_cast<unsigned*>(ws + need + rows_b + state_b);
             if (onecu && a->slab) a->slab = reinterpret_cast<f32x4*>(ws + need + rows_b + state_b + 256);
-            P.params = adam->params; P.m = adam->m; P.v = adam->v; P.mask = adam->mask; P.step_ptr = adam->step_ptr; P.grads = grads;
-            P.opt = adam->opt; P.off_loss = net->lay.off_loss;
+            P.params = tail->params; P.m = tail->m; P.v = tail->v; P.mask = tail->mask; P.step_ptr = tail->step_ptr; P.grads = grads;
+            P.opt = tail->opt; P.off_loss = net->lay.off_loss;
 #ifdef PINN_EMU
             memset(P.sync, 0, 256);
 #else
@@ -976,7 +980,7 @@ static int run_train(pinn_t* net, PinnKArgs* a, const Plan& plan, int nd, float*
             note_launch(plan);
             if (rc == 1) return 0;               // (this instantiation has no such form after all: the caller falls back)
             if (rc) return fail("fit kernel launch failed (%d)", rc);
-            g_fit_persist.done = 1;
+            tail->persist->launched = true;
             g_fit_last_sync = onecu ? nullptr : P.sync;        // (grid form: its timeout flag, read back by pinn_fit_chunk_status)
         }
         return 0;
@@ -1006,7 +1010,7 @@ static int run_train(pinn_t* net, PinnKArgs* a, const Plan& plan, int nd, float*
 #endif
         }
         const int rows = (plan.wgx && net->lay.lh > 0) ? plan.rows() : plan.grid;
-        if (launch_reduce(a->partials, rows, net->lay.p_total, grads, (accumulate || t0 > 0) ? 1 : 0, stream, last ? adam : nullptr))
+        if (launch_reduce(a->partials, rows, net->lay.p_total, grads, (accumulate || t0 > 0) ? 1 : 0, stream, last ? tail : nullptr))
             return 1;
         if (last) break;
     }
@@ -1050,13 +1054,15 @@ static int check_program(const pinn_program_t& pg, int first_temp, int n_consts_
     return 0;
 }
 
-static int residual_step_impl(pinn_t* net, const pinn_residual_t* residual, const float* params, const float* xs,
-                              int64_t n_points, const int* dir_cols, int nd, int n2, const float* ic_streams,
-                              float ic_const, float inv_n_global, float* grads, void* workspace, size_t workspace_bytes,
-                              void* stream, const AdamArgs* adam, int accumulate = 0) {
-    if (!net || !residual || !params || !xs || !grads) return fail("null argument");
+static int residual_step_impl(const StepCall& c, float inv_n_global, const StepTail* tail, int accumulate = 0) {
+    pinn_t* net = c.net;
+    const pinn_residual_t* residual = c.residual;
+    const float* ic_streams = c.ic_streams;
+    const int64_t n_points = c.n_points;
+    const int nd = c.nd, n2 = c.n2;
+    if (!net || !residual || !c.params || !c.xs || !c.grads) return fail("null argument");
     if (n_points <= 0) return fail("n_points must be positive");
-    if (check_dirs(net, dir_cols, nd, n2)) return 1;
+    if (check_dirs(net, c.dir_cols, nd, n2)) return 1;
     if (residual->n_aux < 0 || residual->n_aux > PINN_MAX_AUX) return fail("n_aux=%d outside [0, %d]", residual->n_aux, PINN_MAX_AUX);
     if (residual->kind != PINN_RES_AFFINE && residual->kind != PINN_RES_PROGRAM) return fail("unknown residual kind %d", residual->kind);
     Plan plan;
@@ -1068,7 +1074,7 @@ static int residual_step_impl(pinn_t* net, const pinn_residual_t* residual, cons
     const int d = net->lay.d;
     const int s_user = pinn_ns(nd, n2), s_kernel = pinn_ns(nd, n2k), shift = s_kernel - s_user;
     PinnKArgs a;
-    fill_args(net, &a, params, xs, n_points, dir_cols, nd, n2, ic_streams, ic_const);
+    fill_args(net, &a, c.params, c.xs, n_points, c.dir_cols, nd, n2, ic_streams, c.ic_const);
     a.res_kind = residual->kind;
     a.n_aux = residual->n_aux;
     a.n_vars = residual->n_vars;
@@ -1130,36 +1136,31 @@ static int residual_step_impl(pinn_t* net, const pinn_residual_t* residual, cons
     if (a.crit == PINN_CRIT_SMOOTH_L1 && a.crit_param == 0.0f) a.crit = PINN_CRIT_L1;      // (as torch: smooth_l1_loss with beta 0 is l1_loss)
     if (a.crit == PINN_CRIT_MSE || a.crit == PINN_CRIT_L1) a.crit_param = 0.0f;
     if (make_plan(net, n_points, nd, n2, &plan, PINN_MODE_STEP, residual->kind, comb, &a)) return 1;      // with the call's own arguments
-    return run_train(net, &a, plan, nd, grads, accumulate, workspace, workspace_bytes, stream, &residual->pre, adam, residual->pre_consts64);
+    return run_train(net, &a, plan, nd, c.grads, accumulate, c.workspace, c.workspace_bytes, c.stream, &residual->pre, tail, residual->pre_consts64);
 }
 
 int pinn_residual_step(pinn_t* net, const pinn_residual_t* residual, const float* params, const float* xs,
                        int64_t n_points, const int* dir_cols, int nd, int n2, const float* ic_streams, float ic_const,
                        float inv_n_global, float* grads, void* workspace, size_t workspace_bytes, void* stream) {
-    return residual_step_impl(net, residual, params, xs, n_points, dir_cols, nd, n2, ic_streams, ic_const, inv_n_global,
-                              grads, workspace, workspace_bytes, stream, nullptr);
+    const StepCall c = {net, residual, params, xs, n_points, dir_cols, nd, n2, ic_streams, ic_const, grads, workspace, workspace_bytes, stream};
+    return residual_step_impl(c, inv_n_global, nullptr);
 }
 
 int pinn_residual_step_add(pinn_t* net, const pinn_residual_t* residual, const float* params, const float* xs,
                            int64_t n_points, const int* dir_cols, int nd, int n2, const float* ic_streams, float ic_const,
                            float inv_n_global, float* grads, void* workspace, size_t workspace_bytes, void* stream) {
-    return residual_step_impl(net, residual, params, xs, n_points, dir_cols, nd, n2, ic_streams, ic_const, inv_n_global,
-                              grads, workspace, workspace_bytes, stream, nullptr, 1);
+    const StepCall c = {net, residual, params, xs, n_points, dir_cols, nd, n2, ic_streams, ic_const, grads, workspace, workspace_bytes, stream};
+    return residual_step_impl(c, inv_n_global, nullptr, 1);
 }
 
-// one whole iteration with the update of `opt` in the last reduction launch (the Adam entry points hand in plain_adam(...): Adam's four
+// one whole iteration with the update of `tail` in the last reduction launch (the Adam entry points hand in plain_adam(...): Adam's four
 // numbers travel as they always did, unchecked; the family's entry points go through optim_prepare first)
-static int residual_optim_step(pinn_t* net, const pinn_residual_t* residual, float* params, const float* xs,
-                               int64_t n_points, const int* dir_cols, int nd, int n2, const float* ic_streams,
-                               float ic_const, float* grads, float* exp_avg, float* exp_avg_sq, const uint8_t* mask,
-                               int32_t* step_ptr, int32_t step, const PinnOptK& opt,
-                               float* loss_out, void* workspace, size_t workspace_bytes, void* stream) {
-    if (!net || !exp_avg || !exp_avg_sq || !step_ptr) return fail("null argument");
-    if (step < 1) return fail("step must be >= 1");
-    AdamArgs adam = {params, exp_avg, exp_avg_sq, mask, step_ptr, step, opt, loss_out, net->lay.off_loss};
+static int residual_optim_step(const StepCall& c, StepTail* tail) {
+    if (!c.net || !tail->m || !tail->v || !tail->step_ptr) return fail("null argument");
+    if (tail->step_value < 1) return fail("step must be >= 1");
+    tail->off_loss = c.net->lay.off_loss;
     // (reduction='sum', pinn_residual_t::crit_sum: no division by the number of points)
-    return residual_step_impl(net, residual, params, xs, n_points, dir_cols, nd, n2, ic_streams, ic_const,
-                              (residual && residual->crit_sum) ? 1.0f : 1.0f / (float)n_points, grads, workspace, workspace_bytes, stream, &adam);
+    return residual_step_impl(c, (c.residual && c.residual->crit_sum) ? 1.0f : 1.0f / (float)c.n_points, tail);
 }
 
 int pinn_residual_adam_step(pinn_t* net, const pinn_residual_t* residual, float* params, const float* xs,
@@ -1167,8 +1168,9 @@ int pinn_residual_adam_step(pinn_t* net, const pinn_residual_t* residual, float*
                             float ic_const, float* grads, float* exp_avg, float* exp_avg_sq, const uint8_t* mask,
                             int32_t* step_ptr, int32_t step, float lr, float beta1, float beta2, float eps,
                             float* loss_out, void* workspace, size_t workspace_bytes, void* stream) {
-    return residual_optim_step(net, residual, params, xs, n_points, dir_cols, nd, n2, ic_streams, ic_const, grads, exp_avg, exp_avg_sq, mask,
-                               step_ptr, step, plain_adam(lr, beta1, beta2, eps), loss_out, workspace, workspace_bytes, stream);
+    const StepCall c = {net, residual, params, xs, n_points, dir_cols, nd, n2, ic_streams, ic_const, grads, workspace, workspace_bytes, stream};
+    StepTail tail = update_tail({params, exp_avg, exp_avg_sq, mask, step_ptr}, step, plain_adam(lr, beta1, beta2, eps), loss_out);
+    return residual_optim_step(c, &tail);
 }
 
 int pinn_residual_optim_step(pinn_t* net, const pinn_residual_t* residual, float* params, const float* xs,
@@ -1178,72 +1180,80 @@ int pinn_residual_optim_step(pinn_t* net, const pinn_residual_t* residual, float
                              size_t workspace_bytes, void* stream) {
     PinnOptK k;
     if (optim_prepare(opt, &k)) return 1;
-    return residual_optim_step(net, residual, params, xs, n_points, dir_cols, nd, n2, ic_streams, ic_const, grads, exp_avg, exp_avg_sq, mask,
-                               step_ptr, step, k, loss_out, workspace, workspace_bytes, stream);
+    const StepCall c = {net, residual, params, xs, n_points, dir_cols, nd, n2, ic_streams, ic_const, grads, workspace, workspace_bytes, stream};
+    StepTail tail = update_tail({params, exp_avg, exp_avg_sq, mask, step_ptr}, step, k, loss_out);
+    return residual_optim_step(c, &tail);
 }
 
 // the sampler description of a fit chunk in the form the reduction's tail takes (non-zero: columns it cannot draw)
-static int fit_next_spec(const pinn_net* net, float* xs, int64_t n_points, const int* kind, const float* a, const float* b, uint64_t seed,
-                         PinnNextBatch* out) {
-    if (!net || !xs || !kind || !a || !b || n_points <= 0 || net->lay.d < 1 || net->lay.d > PINN_MAX_INPUTS) return 1;
+static int fit_next_spec(const FitCall& f, PinnNextBatch* out) {
+    const pinn_net* net = f.step.net;
+    if (!net || !f.xs || !f.kind || !f.a || !f.b || f.step.n_points <= 0 || net->lay.d < 1 || net->lay.d > PINN_MAX_INPUTS) return 1;
     memset(out, 0, sizeof(*out));
-    out->xs = xs; out->n = (long long)n_points; out->spec.d = net->lay.d;
+    out->xs = f.xs; out->n = (long long)f.step.n_points; out->spec.d = net->lay.d;
     for (int c = 0; c < net->lay.d; ++c) {
-        if (kind[c] < PINN_SAMPLE_UNIFORM || kind[c] > PINN_SAMPLE_CONST) return 1;
-        out->spec.kind[c] = kind[c]; out->spec.a[c] = a[c]; out->spec.b[c] = b[c];
+        if (f.kind[c] < PINN_SAMPLE_UNIFORM || f.kind[c] > PINN_SAMPLE_CONST) return 1;
+        out->spec.kind[c] = f.kind[c]; out->spec.a[c] = f.a[c]; out->spec.b[c] = f.b[c];
     }
-    out->k0 = (unsigned)(seed & 0xffffffffull); out->k1 = (unsigned)(seed >> 32);
+    out->k0 = (unsigned)(f.seed & 0xffffffffull); out->k1 = (unsigned)(f.seed >> 32);
     return 0;
 }
 
 // does a fused step of this batch run as ONE tile pass + ONE reduction (not chunk by chunk)?
-static bool single_pass_step(pinn_net* net, const pinn_residual_t* residual, int64_t n_points, int nd, int n2) {
-    if (!residual) return false;
+static bool single_pass_step(const StepCall& c) {
+    if (!c.residual) return false;
     Plan plan;
-    const int comb = residual->combined ? 1 : 0;
-    if (make_plan(net, n_points, nd, n2, &plan, PINN_MODE_STEP, residual->kind, comb, nullptr)) return false;
+    if (make_plan(c.net, c.n_points, c.nd, c.n2, &plan, PINN_MODE_STEP, c.residual->kind, c.residual->combined ? 1 : 0, nullptr)) return false;
     return plan.chunk_tiles >= plan.ntiles;
 }
 
-static int fit_steps_impl(pinn_t* net, const pinn_residual_t* residual, float* params, float* xs, int64_t n_points,
-                          const int* kind, const float* a, const float* b, uint64_t seed, uint64_t call_index0,
-                          const int* dir_cols, int nd, int n2, float ic_const, float* grads, float* exp_avg, float* exp_avg_sq,
-                          const uint8_t* mask, int32_t* step_ptr, int32_t step0, const PinnOptK& opt,
-                          float* loss_history, int32_t k_steps, void* workspace, size_t workspace_bytes, void* stream,
-                          const float* lr_steps = nullptr) {
-    if (!net || !xs || !loss_history) return fail("null argument");
-    if (k_steps < 0 || step0 < 1) return fail("k_steps must be >= 0 and step0 >= 1");
-    if (check_lr_steps(lr_steps, k_steps)) return 1;
-    // K iterations of the reference's fit loop (model_torch.py:426-464) enqueued by ONE call: sample, fused step, Adam. Nothing
-    // here waits for the device; the arguments that change from one iteration to the next (Philox batch counter, Adam step,
-    // slot of the loss history) travel by value, so a launch graph would have to be re-instantiated per iteration anyway
-    // from the second iteration on the batch is drawn by the reduction launch of the iteration before (pinn_reduce_kernel's tail: the
-    // tile kernel of that iteration is through with the buffer), which saves every iteration one dependent launch -- where the step
-    // is one pass (a chunked WGX step reduces several times per iteration: those keep the sampler launch)
+// K iterations of the reference's fit loop (model_torch.py:426-464): sample, fused step, update. Nothing here waits for the device.
+// `capture` nullptr, the eager loop on `stream`: what changes from one iteration to the next (Philox batch counter, step, slot of the loss
+// history) travels by value. `capture` a control block, the same loop recorded on a capturing `stream`: those values are placeholders
+// (0, 1, loss_history) and the launches read the real ones from the block at index k.
+// From the second iteration on the batch is drawn by the reduction launch of the iteration before (pinn_reduce_kernel's tail: the tile
+// kernel of that iteration is through with the buffer), which saves every iteration one dependent launch -- where the step is one pass
+// (a chunked WGX step reduces several times per iteration: those keep the sampler launch). The LAST reduction draws nothing.
+static int enqueue_chunk(const FitCall& f, void* stream, const PinnFitCtrl* capture) {
+    StepCall c = f.step;
+    c.stream = stream;
     PinnNextBatch next = {nullptr, 0, {}, 0u, 0u, 0ull};
-    const bool hand_over = fit_next_spec(net, xs, n_points, kind, a, b, seed, &next) == 0 && single_pass_step(net, residual, n_points, nd, n2);
+    const bool hand_over = fit_next_spec(f, &next) == 0 && single_pass_step(c);
     int rc = 0;
-    for (int32_t k = 0; k < k_steps && !rc; ++k) {
-        if (k == 0 || !hand_over) rc = pinn_sample_points(xs, n_points, net->lay.d, kind, a, b, seed, call_index0 + (uint64_t)k, stream);
+    for (int32_t k = 0; k < f.k_steps && !rc; ++k) {
+        const uint64_t call = capture ? 0 : f.call_index0 + (uint64_t)k;
+        const int capture_k = capture ? k : 0;
+        if (k == 0 || !hand_over) rc = sample_points(f.xs, c.n_points, c.net->lay.d, f.kind, f.a, f.b, f.seed, call, stream, capture, capture_k);
         if (rc) break;
-        if (hand_over && k + 1 < k_steps) { next.call = call_index0 + (uint64_t)k + 1; g_fit_next = next; }
         // (a schedule: iteration k is the step of pinn_residual_optim_step with opt->lr = lr_steps[k])
-        rc = residual_optim_step(net, residual, params, xs, n_points, dir_cols, nd, n2, nullptr, ic_const, grads, exp_avg,
-                                 exp_avg_sq, mask, step_ptr, step0 + k, lr_steps ? optim_at_rate(opt, lr_steps[k]) : opt, loss_history + k,
-                                 workspace, workspace_bytes, stream);
-        g_fit_next.n = 0;
+        StepTail tail = capture ? update_tail(f.state, 1, f.opt, f.loss_history)
+                                : update_tail(f.state, f.step0 + k, f.lr_steps ? optim_at_rate(f.opt, f.lr_steps[k]) : f.opt, f.loss_history + k);
+        if (hand_over && k + 1 < f.k_steps) { tail.next = next; tail.next.call = capture ? 0 : call + 1; }
+        tail.capture = capture; tail.capture_k = capture_k;
+        rc = residual_optim_step(c, &tail);
     }
     return rc;
 }
+
+static int fit_steps_eager(const FitCall& f) {
+    if (!f.step.net || !f.xs || !f.loss_history) return fail("null argument");
+    if (f.k_steps < 0 || f.step0 < 1) return fail("k_steps must be >= 0 and step0 >= 1");
+    if (check_lr_steps(f.lr_steps, f.k_steps)) return 1;
+    return enqueue_chunk(f, f.step.stream, nullptr);
+}
+
+// the record of a pinn_fit_steps* call from the parameter names all five entry points share; what differs between them comes as arguments
+#define PINN_FIT_CALL(optk, ctrl_, ctrl_bytes_, lr_steps_)                                                                                   \
+    {{net, residual, params, xs, n_points, dir_cols, nd, n2, nullptr, ic_const, grads, workspace, workspace_bytes, stream},                   \
+     xs, kind, a, b, seed, call_index0, {params, exp_avg, exp_avg_sq, mask, step_ptr}, step0, optk, loss_history, k_steps, ctrl_, ctrl_bytes_, lr_steps_}
 
 int pinn_fit_steps(pinn_t* net, const pinn_residual_t* residual, float* params, float* xs, int64_t n_points,
                    const int* kind, const float* a, const float* b, uint64_t seed, uint64_t call_index0,
                    const int* dir_cols, int nd, int n2, float ic_const, float* grads, float* exp_avg, float* exp_avg_sq,
                    const uint8_t* mask, int32_t* step_ptr, int32_t step0, float lr, float beta1, float beta2, float eps,
                    float* loss_history, int32_t k_steps, void* workspace, size_t workspace_bytes, void* stream) {
-    return fit_steps_impl(net, residual, params, xs, n_points, kind, a, b, seed, call_index0, dir_cols, nd, n2, ic_const, grads, exp_avg,
-                          exp_avg_sq, mask, step_ptr, step0, plain_adam(lr, beta1, beta2, eps), loss_history, k_steps, workspace,
-                          workspace_bytes, stream);
+    const FitCall f = PINN_FIT_CALL(plain_adam(lr, beta1, beta2, eps), nullptr, 0, nullptr);
+    return fit_steps_eager(f);
 }
 
 int pinn_fit_steps_optim(pinn_t* net, const pinn_residual_t* residual, float* params, float* xs, int64_t n_points,
@@ -1253,8 +1263,8 @@ int pinn_fit_steps_optim(pinn_t* net, const pinn_residual_t* residual, float* pa
                          float* loss_history, int32_t k_steps, void* workspace, size_t workspace_bytes, void* stream) {
     PinnOptK k;
     if (optim_prepare(opt, &k)) return 1;
-    return fit_steps_impl(net, residual, params, xs, n_points, kind, a, b, seed, call_index0, dir_cols, nd, n2, ic_const, grads, exp_avg,
-                          exp_avg_sq, mask, step_ptr, step0, k, loss_history, k_steps, workspace, workspace_bytes, stream);
+    const FitCall f = PINN_FIT_CALL(k, nullptr, 0, nullptr);
+    return fit_steps_eager(f);
 }
 
 size_t pinn_fit_ctrl_bytes(void) { return sizeof(PinnFitCtrl); }
@@ -1266,6 +1276,35 @@ int pinn_debug_fit_graph_stats(int32_t out[4]) {
     return 0;
 }
 
+static int launch_fit_ctrl(const FitCall& f) {
+    PinnFitCtrlArgs ca;
+    fit_ctrl_fill(&ca, f);
+    return launch("control-block", pinn_fit_ctrl_kernel, 1, 128, 0, f.step.stream, reinterpret_cast<PinnFitCtrl*>(f.ctrl), ca);
+}
+
+// narrow nets, batches of a few tiles: the whole chunk -- any length up to PINN_FIT_CHUNK_MAX -- as ONE launch (pinn_fit_kernel.h); the
+// eager loop's trajectory to fp32 round-off. `launched` false with 0 returned: the chunk does not qualify and is still to be run
+static int try_one_launch_chunk(const FitCall& f, bool* launched) {
+    const pinn_net* net = f.step.net;
+    *launched = false;
+    OneLaunch one;
+    memset(&one, 0, sizeof(one));
+    PinnNextBatch spec_probe = {nullptr, 0, {}, 0u, 0u, 0ull};
+    if (net->fit_persistent && net->lay.hp <= 32 && f.ctrl && f.ctrl_bytes >= sizeof(PinnFitCtrl) && f.k_steps >= 1 && f.k_steps <= PINN_FIT_CHUNK_MAX &&
+        !g_profile && !g_phase_prof && f.step.residual && f.state.params && f.step.grads && f.state.exp_avg && f.state.exp_avg_sq && f.state.step_ptr &&
+        fit_next_spec(f, &spec_probe) == 0) {
+        PinnFitP& P = one.p;
+        P.ctrl = reinterpret_cast<PinnFitCtrl*>(f.ctrl); P.k_steps = f.k_steps; P.xs = f.xs; P.n = (long long)f.step.n_points; P.spec = spec_probe.spec;
+        if (launch_fit_ctrl(f)) return 1;
+        StepTail tail = update_tail(f.state, f.step0, f.opt, f.loss_history);
+        tail.persist = &one;
+        if (const int rc = residual_optim_step(f.step, &tail)) return rc;
+        if (one.launched) { ++g_fit_graph_stats[0]; *launched = true; }         // (counted with the replayed chunks: one launch for the chunk)
+    }
+    return 0;
+}
+
+#ifndef PINN_EMU
 // FNV-1a over the bytes of everything a captured chunk depends on
 static void key_mix(unsigned long long (&key)[4], const void* p, size_t n) {
     const unsigned char* b = reinterpret_cast<const unsigned char*>(p);
@@ -1275,136 +1314,100 @@ static void key_mix(unsigned long long (&key)[4], const void* p, size_t n) {
     }
 }
 
-static int fit_steps_graph_impl(pinn_t* net, const pinn_residual_t* residual, float* params, float* xs, int64_t n_points,
-                                const int* kind, const float* a, const float* b, uint64_t seed, uint64_t call_index0,
-                                const int* dir_cols, int nd, int n2, float ic_const, float* grads, float* exp_avg, float* exp_avg_sq,
-                                const uint8_t* mask, int32_t* step_ptr, int32_t step0, const PinnOptK& opt,
-                                float* loss_history, int32_t k_steps, void* workspace, size_t workspace_bytes, void* ctrl,
-                                size_t ctrl_bytes, void* stream, const float* lr_steps = nullptr) {
-    if (!net || !residual || !xs || !loss_history || !kind || !a || !b || !dir_cols) return fail("null argument");
-    if (k_steps < 0 || step0 < 1) return fail("k_steps must be >= 0 and step0 >= 1");
-    if (check_lr_steps(lr_steps, k_steps)) return 1;
-    // narrow nets, batches of a few tiles: the whole chunk -- any length up to PINN_FIT_CHUNK_MAX -- as ONE launch (pinn_fit_kernel.h);
-    // the eager loop's trajectory to fp32 round-off
-    if (net->fit_persistent && net->lay.hp <= 32 && ctrl && ctrl_bytes >= sizeof(PinnFitCtrl) && k_steps >= 1 && k_steps <= PINN_FIT_CHUNK_MAX &&
-        !g_profile && !g_phase_prof && residual && params && grads && exp_avg && exp_avg_sq && step_ptr) {
-        PinnNextBatch spec_probe = {nullptr, 0, {}, 0u, 0u, 0ull};
-        if (fit_next_spec(net, xs, n_points, kind, a, b, seed, &spec_probe) == 0) {
-            PinnFitCtrl* dctrl = reinterpret_cast<PinnFitCtrl*>(ctrl);
-            PinnFitCtrlArgs ca;
-            fit_ctrl_fill(&ca, call_index0, loss_history, step0, seed, opt, lr_steps, k_steps);
-            memset(&g_fit_persist, 0, sizeof(g_fit_persist));
-            PinnFitP& P = g_fit_persist.p;
-            P.ctrl = dctrl; P.k_steps = k_steps; P.xs = xs; P.n = (long long)n_points; P.spec = spec_probe.spec;
-            g_fit_persist.active = 1;
-#ifdef PINN_EMU
-            emu::launch(1, 128, 0, [&] { pinn_fit_ctrl_kernel(dctrl, ca); });
-            const int rc0 = 0;
-#else
-            hipLaunchKernelGGL(pinn_fit_ctrl_kernel, dim3(1), dim3(128), 0, (hipStream_t)stream, dctrl, ca);
-            const int rc0 = (hipGetLastError() != hipSuccess) ? fail("control-block launch failed") : 0;
-#endif
-            const int rc = rc0 ? rc0
-                           : residual_optim_step(net, residual, params, xs, n_points, dir_cols, nd, n2, nullptr, ic_const, grads, exp_avg,
-                                                     exp_avg_sq, mask, step_ptr, step0, opt, loss_history, workspace,
-                                                     workspace_bytes, stream);
-            const int did = g_fit_persist.done;
-            g_fit_persist.active = 0;
-            if (rc) return rc;
-            if (did) { ++g_fit_graph_stats[0]; return 0; }          // (counted with the replayed chunks: one launch for the chunk)
-        }
-    }
-#ifdef PINN_EMU
-    return fit_steps_impl(net, residual, params, xs, n_points, kind, a, b, seed, call_index0, dir_cols, nd, n2, ic_const, grads, exp_avg,
-                          exp_avg_sq, mask, step_ptr, step0, opt, loss_history, k_steps, workspace, workspace_bytes, stream, lr_steps);
-#else
-    // the graph pays where launch gaps are a visible share of an iteration; chunks that do not qualify run the eager loop
-    // (only whole chunks: the tail of a fit would capture a graph of its own that nothing replays)
-    if (k_steps != PINN_FIT_CHUNK_MAX || !ctrl || ctrl_bytes < sizeof(PinnFitCtrl) || g_profile || g_phase_prof)
-        return fit_steps_impl(net, residual, params, xs, n_points, kind, a, b, seed, call_index0, dir_cols, nd, n2, ic_const, grads, exp_avg,
-                              exp_avg_sq, mask, step_ptr, step0, opt, loss_history, k_steps, workspace, workspace_bytes, stream, lr_steps);
-    // everything the captured launches carry BY VALUE or by address (the per-iteration values travel through the control block)
-    unsigned long long key[4] = {14695981039346656037ull, 14695981039346656037ull ^ 1, 14695981039346656037ull ^ 2, 14695981039346656037ull ^ 3};
-    key_mix(key, residual, sizeof(*residual));
-    const void* ptrs[] = {params, xs, grads, exp_avg, exp_avg_sq, mask, step_ptr, workspace, ctrl, stream};
+// everything the captured launches carry BY VALUE or by address (the per-iteration values travel through the control block)
+static void chunk_replay_key(const FitCall& f, int dev, unsigned long long (&key)[4]) {
+    const StepCall& c = f.step;
+    const pinn_net* net = c.net;
+    const unsigned long long seed[4] = {14695981039346656037ull, 14695981039346656037ull ^ 1, 14695981039346656037ull ^ 2, 14695981039346656037ull ^ 3};
+    memcpy(key, seed, sizeof(seed));
+    key_mix(key, c.residual, sizeof(*c.residual));
+    const void* ptrs[] = {f.state.params, f.xs, c.grads, f.state.exp_avg, f.state.exp_avg_sq, f.state.mask, f.state.step_ptr, c.workspace, f.ctrl, c.stream};
     key_mix(key, ptrs, sizeof(ptrs));
     // (not the sampler's key `seed`: it travels through the control block, so the chunk recorded by one fit call is replayed by the next)
-    const long long ints[] = {(long long)n_points, nd, n2, (long long)workspace_bytes, net->gemm_mode, net->tanh_mode, net->max_per_cu,
+    const long long ints[] = {(long long)c.n_points, c.nd, c.n2, (long long)c.workspace_bytes, net->gemm_mode, net->tanh_mode, net->max_per_cu,
                               net->prepass_in_kernel, (long long)net->wgx_chunk_bytes};
     key_mix(key, ints, sizeof(ints));
-    const float flts[] = {ic_const, residual->crit_param};
+    const float flts[] = {c.ic_const, c.residual->crit_param};
     // (the update rule with its hyper-parameters: the reductions of the recorded chunk carry it by value. Under a control block they
     //  read the learning rate and what derives from it -- step_size, decay -- from the block, never from that copy: a call with a
     //  schedule keys on the rule WITHOUT them, so chunks that differ only in their rates replay one recording)
-    PinnOptK key_opt = opt;
-    if (lr_steps) { key_opt.lr = 0.0f; key_opt.decay = 0.0f; key_opt.pad = 1; }
+    PinnOptK key_opt = f.opt;
+    if (f.lr_steps) { key_opt.lr = 0.0f; key_opt.decay = 0.0f; key_opt.pad = 1; }
     key_mix(key, &key_opt, sizeof(key_opt));
     // (the criterion is part of `residual`, hashed above; named here once more so that the key does not depend on where the fields sit)
-    const int crit_key[] = {residual->criterion, residual->crit_sum};
+    const int crit_key[] = {c.residual->criterion, c.residual->crit_sum};
     key_mix(key, crit_key, sizeof(crit_key));
     key_mix(key, flts, sizeof(flts));
-    key_mix(key, kind, sizeof(int) * net->lay.d); key_mix(key, a, sizeof(float) * net->lay.d); key_mix(key, b, sizeof(float) * net->lay.d);
-    key_mix(key, dir_cols, sizeof(int) * (nd > 0 ? nd : 0));
+    key_mix(key, f.kind, sizeof(int) * net->lay.d); key_mix(key, f.a, sizeof(float) * net->lay.d); key_mix(key, f.b, sizeof(float) * net->lay.d);
+    key_mix(key, c.dir_cols, sizeof(int) * (c.nd > 0 ? c.nd : 0));
+    key_mix(key, &dev, sizeof(dev));
+}
+
+// record the chunk as a launch graph for the next chunks to replay. 0 also where the runtime refuses the capture (counted in
+// g_fit_graph_stats): the chunk at hand has already run eagerly
+static int capture_chunk(const FitCall& f, int dev, const unsigned long long (&key)[4]) {
+    pinn_net* net = f.step.net;
+    hipGraph_t graph = nullptr;
+    // capture happens on a stream of the library's own (torch's current stream is usually the legacy default stream, which cannot
+    // capture); nothing EXECUTES on it -- the nodes are kernel launches without a stream of their own, the graph is launched on the caller's
+    static thread_local hipStream_t cap_streams[64] = {nullptr};
+    hipStream_t& cs = cap_streams[dev & 63];
+    if (!cs && hipStreamCreateWithFlags(&cs, hipStreamNonBlocking) != hipSuccess) { (void)hipGetLastError(); ++g_fit_graph_stats[2]; return 0; }
+    const hipError_t be = hipStreamBeginCapture(cs, hipStreamCaptureModeThreadLocal);
+    if (be != hipSuccess) { (void)hipGetLastError(); ++g_fit_graph_stats[2]; g_fit_graph_stats[3] = (int)be; return 0; }
+    const int crc = enqueue_chunk(f, cs, reinterpret_cast<PinnFitCtrl*>(f.ctrl));
+    const hipError_t ce = hipStreamEndCapture(cs, &graph);
+    if (crc || ce != hipSuccess || !graph) {
+        (void)hipGetLastError(); ++g_fit_graph_stats[2]; g_fit_graph_stats[3] = crc ? -crc : (int)ce;
+        if (graph) (void)hipGraphDestroy(graph);
+        return crc ? crc : 0;
+    }
+    hipGraphExec_t exec = nullptr;
+    const hipError_t ie = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
+    if (ie != hipSuccess) { (void)hipGetLastError(); ++g_fit_graph_stats[2]; g_fit_graph_stats[3] = (int)ie; (void)hipGraphDestroy(graph); return 0; }
+    (void)hipGraphDestroy(graph);
+    net->fit_graph_exec = exec;
+    ++g_fit_graph_stats[1];
+    net->fit_graph_k = f.k_steps;
+    memcpy(net->fit_graph_key, key, sizeof(key));
+    return 0;
+}
+
+// the graph pays where launch gaps are a visible share of an iteration; chunks that do not qualify run the eager loop
+// (only whole chunks: the tail of a fit would capture a graph of its own that nothing replays)
+static int replay_chunk(const FitCall& f) {
+    pinn_net* net = f.step.net;
+    if (f.k_steps != PINN_FIT_CHUNK_MAX || !f.ctrl || f.ctrl_bytes < sizeof(PinnFitCtrl) || g_profile || g_phase_prof) return fit_steps_eager(f);
     int dev = 0;
     (void)hipGetDevice(&dev);
-    key_mix(key, &dev, sizeof(dev));
-    PinnFitCtrl* dctrl = reinterpret_cast<PinnFitCtrl*>(ctrl);
-    hipStream_t hs = (hipStream_t)stream;
-    const bool hit = net->fit_graph_exec && net->fit_graph_k == k_steps && memcmp(key, net->fit_graph_key, sizeof(key)) == 0;
+    unsigned long long key[4];
+    chunk_replay_key(f, dev, key);
+    const bool hit = net->fit_graph_exec && net->fit_graph_k == f.k_steps && memcmp(key, net->fit_graph_key, sizeof(key)) == 0;
     if (!hit) {
         if (net->fit_graph_exec) { (void)hipGraphExecDestroy((hipGraphExec_t)net->fit_graph_exec); net->fit_graph_exec = nullptr; }
         // one eager iteration's worth of planning has to have happened (function attributes, occupancy queries are not capturable):
         // the first chunk of a configuration runs eagerly AND is followed by the capture of the graph the next chunks replay
-        const int rc = fit_steps_impl(net, residual, params, xs, n_points, kind, a, b, seed, call_index0, dir_cols, nd, n2, ic_const, grads,
-                                      exp_avg, exp_avg_sq, mask, step_ptr, step0, opt, loss_history, k_steps, workspace,
-                                      workspace_bytes, stream, lr_steps);
-        if (rc) return rc;
-        hipGraph_t graph = nullptr;
-        // capture happens on a stream of the library's own (torch's current stream is usually the legacy default stream, which cannot
-        // capture); nothing EXECUTES on it -- the nodes are kernel launches without a stream of their own, the graph is launched on `hs`
-        static thread_local hipStream_t cap_streams[64] = {nullptr};
-        hipStream_t& cs = cap_streams[dev & 63];
-        if (!cs && hipStreamCreateWithFlags(&cs, hipStreamNonBlocking) != hipSuccess) { (void)hipGetLastError(); ++g_fit_graph_stats[2]; return 0; }
-        const hipError_t be = hipStreamBeginCapture(cs, hipStreamCaptureModeThreadLocal);
-        if (be != hipSuccess) { (void)hipGetLastError(); ++g_fit_graph_stats[2]; g_fit_graph_stats[3] = (int)be; return 0; }
-        int crc = 0;
-        PinnNextBatch cap_next = {nullptr, 0, {}, 0u, 0u, 0ull};
-        const bool cap_hand_over = fit_next_spec(net, xs, n_points, kind, a, b, seed, &cap_next) == 0 && single_pass_step(net, residual, n_points, nd, n2);
-        for (int32_t k = 0; k < k_steps && !crc; ++k) {
-            g_fit_capture = {dctrl, k};
-            // (the by-value step numbers and loss slots of the captured launches are placeholders: the kernels read the control block)
-            if (k == 0 || !cap_hand_over) crc = pinn_sample_points(xs, n_points, net->lay.d, kind, a, b, seed, 0, cs);
-            if (cap_hand_over && k + 1 < k_steps) g_fit_next = cap_next;
-            if (!crc) crc = residual_optim_step(net, residual, params, xs, n_points, dir_cols, nd, n2, nullptr, ic_const, grads, exp_avg,
-                                                    exp_avg_sq, mask, step_ptr, 1, opt, loss_history, workspace,
-                                                    workspace_bytes, cs);
-            g_fit_next.n = 0;       // (as in the eager loop: the LAST reduction of a chunk draws nothing -- ADVICE r4)
-        }
-        g_fit_capture = {nullptr, 0};
-        g_fit_next.n = 0;
-        const hipError_t ce = hipStreamEndCapture(cs, &graph);
-        if (crc || ce != hipSuccess || !graph) {
-            (void)hipGetLastError(); ++g_fit_graph_stats[2]; g_fit_graph_stats[3] = crc ? -crc : (int)ce;
-            if (graph) (void)hipGraphDestroy(graph);
-            return crc ? crc : 0;
-        }
-        hipGraphExec_t exec = nullptr;
-        const hipError_t ie = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
-        if (ie != hipSuccess) { (void)hipGetLastError(); ++g_fit_graph_stats[2]; g_fit_graph_stats[3] = (int)ie; (void)hipGraphDestroy(graph); return 0; }
-        (void)hipGraphDestroy(graph);
-        net->fit_graph_exec = exec;
-        ++g_fit_graph_stats[1];
-        net->fit_graph_k = k_steps;
-        memcpy(net->fit_graph_key, key, sizeof(key));
-        return 0;                   // (this chunk ran eagerly above)
+        if (const int rc = fit_steps_eager(f)) return rc;
+        return capture_chunk(f, dev, key);
     }
-    PinnFitCtrlArgs ca;
-    fit_ctrl_fill(&ca, call_index0, loss_history, step0, seed, opt, lr_steps, k_steps);
-    hipLaunchKernelGGL(pinn_fit_ctrl_kernel, dim3(1), dim3(128), 0, hs, dctrl, ca);
-    if (hipGetLastError() != hipSuccess) return fail("control-block launch failed");
-    if (hipGraphLaunch((hipGraphExec_t)net->fit_graph_exec, hs) != hipSuccess) return fail("hipGraphLaunch failed");
+    if (launch_fit_ctrl(f)) return 1;
+    if (hipGraphLaunch((hipGraphExec_t)net->fit_graph_exec, (hipStream_t)f.step.stream) != hipSuccess) return fail("hipGraphLaunch failed");
     ++g_fit_graph_stats[0];
     return 0;
+}
+#endif
+
+static int fit_steps_graph_impl(const FitCall& f) {
+    if (!f.step.net || !f.step.residual || !f.xs || !f.loss_history || !f.kind || !f.a || !f.b || !f.step.dir_cols) return fail("null argument");
+    if (f.k_steps < 0 || f.step0 < 1) return fail("k_steps must be >= 0 and step0 >= 1");
+    if (check_lr_steps(f.lr_steps, f.k_steps)) return 1;
+    bool launched = false;
+    if (const int rc = try_one_launch_chunk(f, &launched)) return rc;
+    if (launched) return 0;
+#ifdef PINN_EMU
+    return fit_steps_eager(f);      // (no launch graphs in the emulator)
+#else
+    return replay_chunk(f);
 #endif
 }
 
@@ -1414,9 +1417,8 @@ int pinn_fit_steps_graph(pinn_t* net, const pinn_residual_t* residual, float* pa
                          const uint8_t* mask, int32_t* step_ptr, int32_t step0, float lr, float beta1, float beta2, float eps,
                          float* loss_history, int32_t k_steps, void* workspace, size_t workspace_bytes, void* ctrl,
                          size_t ctrl_bytes, void* stream) {
-    return fit_steps_graph_impl(net, residual, params, xs, n_points, kind, a, b, seed, call_index0, dir_cols, nd, n2, ic_const, grads, exp_avg,
-                                exp_avg_sq, mask, step_ptr, step0, plain_adam(lr, beta1, beta2, eps), loss_history, k_steps, workspace,
-                                workspace_bytes, ctrl, ctrl_bytes, stream);
+    const FitCall f = PINN_FIT_CALL(plain_adam(lr, beta1, beta2, eps), ctrl, ctrl_bytes, nullptr);
+    return fit_steps_graph_impl(f);
 }
 
 int pinn_fit_steps_optim_graph(pinn_t* net, const pinn_residual_t* residual, float* params, float* xs, int64_t n_points,
@@ -1427,9 +1429,8 @@ int pinn_fit_steps_optim_graph(pinn_t* net, const pinn_residual_t* residual, flo
                                size_t ctrl_bytes, void* stream) {
     PinnOptK k;
     if (optim_prepare(opt, &k)) return 1;
-    return fit_steps_graph_impl(net, residual, params, xs, n_points, kind, a, b, seed, call_index0, dir_cols, nd, n2, ic_const, grads, exp_avg,
-                                exp_avg_sq, mask, step_ptr, step0, k, loss_history, k_steps, workspace, workspace_bytes, ctrl, ctrl_bytes,
-                                stream);
+    const FitCall f = PINN_FIT_CALL(k, ctrl, ctrl_bytes, nullptr);
+    return fit_steps_graph_impl(f);
 }
 
 int pinn_fit_steps_optim_sched(pinn_t* net, const pinn_residual_t* residual, float* params, float* xs, int64_t n_points,
@@ -1440,10 +1441,10 @@ int pinn_fit_steps_optim_sched(pinn_t* net, const pinn_residual_t* residual, flo
                                size_t ctrl_bytes, void* stream, const float* lr_steps) {
     PinnOptK k;
     if (optim_prepare(opt, &k)) return 1;
-    return fit_steps_graph_impl(net, residual, params, xs, n_points, kind, a, b, seed, call_index0, dir_cols, nd, n2, ic_const, grads, exp_avg,
-                                exp_avg_sq, mask, step_ptr, step0, k, loss_history, k_steps, workspace, workspace_bytes, ctrl, ctrl_bytes,
-                                stream, lr_steps);
+    const FitCall f = PINN_FIT_CALL(k, ctrl, ctrl_bytes, lr_steps);
+    return fit_steps_graph_impl(f);
 }
+#undef PINN_FIT_CALL
 
 static int optim_launch(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, const uint8_t* mask, int64_t n,
                         int32_t* step_ptr, int32_t step, const PinnOptK& opt, void* stream,
@@ -1453,16 +1454,9 @@ static int optim_launch(float* params, const float* grads, float* exp_avg, float
     const int blocks = (int)((n + 255) / 256);
     float step_size = 0.0f, bc2_sqrt = 1.0f;
     if (step > 0) optim_scalars(opt, (double)step, &step_size, &bc2_sqrt);
-#ifdef PINN_EMU
-    if (step <= 0) emu::launch(1, 64, 0, [&] { pinn_tick_kernel(step_ptr); });
-    emu::launch(blocks, 256, 0, [&] { pinn_optim_kernel(params, grads, exp_avg, exp_avg_sq, mask, n, step_ptr, step, step_size, bc2_sqrt, opt, loss_out, off_loss); });
-#else
-    if (step <= 0) hipLaunchKernelGGL(pinn_tick_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, step_ptr);
-    hipLaunchKernelGGL(pinn_optim_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, params, grads, exp_avg,
-                       exp_avg_sq, mask, (long long)n, (int*)step_ptr, (int)step, step_size, bc2_sqrt, opt, loss_out, off_loss);
-    if (hipGetLastError() != hipSuccess) return fail("optimizer kernel launch failed");
-#endif
-    return 0;
+    if (step <= 0 && launch("optimizer kernel", pinn_tick_kernel, 1, 64, 0, stream, (int*)step_ptr)) return 1;
+    return launch("optimizer kernel", pinn_optim_kernel, blocks, 256, 0, stream, params, grads, exp_avg, exp_avg_sq, mask, (long long)n,
+                  (int*)step_ptr, (int)step, step_size, bc2_sqrt, opt, loss_out, off_loss);
 }
 
 int pinn_adam_step(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, const uint8_t* mask, int64_t n,
@@ -1509,8 +1503,8 @@ int pinn_reduce_rows(const float* partials, int32_t n_rows, int32_t row_len, flo
     if (optim_prepare(opt, &k)) return 1;
     if (!params || !exp_avg || !exp_avg_sq || !step_ptr) return fail("null argument");
     if (step < 1) return fail("step must be >= 1");
-    AdamArgs adam = {params, exp_avg, exp_avg_sq, mask, step_ptr, step, k, loss_out, loss_out ? off_loss : -1};
-    return launch_reduce(partials, n_rows, row_len, grads, accumulate ? 1 : 0, stream, &adam);
+    const StepTail tail = update_tail({params, exp_avg, exp_avg_sq, mask, step_ptr}, step, k, loss_out, loss_out ? off_loss : -1);
+    return launch_reduce(partials, n_rows, row_len, grads, accumulate ? 1 : 0, stream, &tail);
 }
 
 // ---- L-BFGS direction (pinn_lbfgs_kernels.h): three launches per inner iteration, whatever the history size --------------------------
@@ -1552,12 +1546,7 @@ int pinn_lbfgs_direction(float* params, const float* grads, float* prev_grad, fl
                        lr, tolerance_grad, tolerance_change, static_cast<double*>(ctrl), static_cast<double*>(workspace), rows};
     const size_t smem_dots = 4 * (size_t)rowlen * sizeof(double);
     const size_t smem_fin = ((size_t)rowlen + 7 * (size_t)m + (size_t)m * m) * sizeof(double);
-#ifdef PINN_EMU
-    (void)stream;
-    emu::launch(rows, PINN_LBFGS_THREADS, smem_dots, [&] { pinn_lbfgs_dots_kernel(A); });
-    emu::launch(1, PINN_LBFGS_THREADS, smem_fin, [&] { pinn_lbfgs_finalize_kernel(A); });
-    emu::launch(blocks, PINN_LBFGS_THREADS, 0, [&] { pinn_lbfgs_combine_kernel(A); });
-#else
+#ifndef PINN_EMU
     // (the finalize pass stages the s.y matrix in LDS: above 64 KB from history_size 85; the attribute is raised once per device and size)
     static std::atomic<size_t> fin_attr[64];                  // (host threads may race to their first call: the worst case is the attribute set twice)
     int dev = 0;
@@ -1568,12 +1557,11 @@ int pinn_lbfgs_direction(float* params, const float* grads, float* prev_grad, fl
             return fail("L-BFGS: %zu bytes of LDS for history_size=%d refused", smem_fin, m);
         fin_attr[dev].store(smem_fin, std::memory_order_relaxed);
     }
-    hipLaunchKernelGGL(pinn_lbfgs_dots_kernel, dim3(rows), dim3(PINN_LBFGS_THREADS), smem_dots, (hipStream_t)stream, A);
-    hipLaunchKernelGGL(pinn_lbfgs_finalize_kernel, dim3(1), dim3(PINN_LBFGS_THREADS), smem_fin, (hipStream_t)stream, A);
-    hipLaunchKernelGGL(pinn_lbfgs_combine_kernel, dim3(blocks), dim3(PINN_LBFGS_THREADS), 0, (hipStream_t)stream, A);
-    if (hipGetLastError() != hipSuccess) return fail("L-BFGS kernel launch failed");
 #endif
-    return 0;
+    if (launch("L-BFGS kernel", pinn_lbfgs_dots_kernel, rows, PINN_LBFGS_THREADS, smem_dots, stream, A) ||
+        launch("L-BFGS kernel", pinn_lbfgs_finalize_kernel, 1, PINN_LBFGS_THREADS, smem_fin, stream, A))
+        return 1;
+    return launch("L-BFGS kernel", pinn_lbfgs_combine_kernel, blocks, PINN_LBFGS_THREADS, 0, stream, A);
 }
 
 // ---- residual-adaptive resampler (pinn_aux_kernels.h: three launches; the redraw is the third alone) -----------------------------------
@@ -1611,22 +1599,10 @@ static int resample_launch(const float* pool, const float* r, int64_t m, int d, 
                           ws, ws + PINN_RESAMPLE_HEAD, ws + PINN_RESAMPLE_HEAD + m, ws + PINN_RESAMPLE_HEAD + m + nb, nb};
     const int draw_blocks = (int)((n_out + PINN_RESAMPLE_BLOCK - 1) / PINN_RESAMPLE_BLOCK);
     const size_t smem = (PINN_RESAMPLE_BLOCK / 64) * sizeof(double);
-#ifdef PINN_EMU
-    (void)stream;
-    if (fill) {
-        emu::launch(nb, PINN_RESAMPLE_BLOCK, smem, [&] { pinn_resample_weights_kernel(A); });
-        emu::launch(1, PINN_RESAMPLE_BLOCK, smem, [&] { pinn_resample_offsets_kernel(A); });
-    }
-    if (n_out > 0) emu::launch(draw_blocks, PINN_RESAMPLE_BLOCK, 0, [&] { pinn_resample_draw_kernel(A); });
-#else
-    if (fill) {
-        hipLaunchKernelGGL(pinn_resample_weights_kernel, dim3(nb), dim3(PINN_RESAMPLE_BLOCK), smem, (hipStream_t)stream, A);
-        hipLaunchKernelGGL(pinn_resample_offsets_kernel, dim3(1), dim3(PINN_RESAMPLE_BLOCK), smem, (hipStream_t)stream, A);
-    }
-    if (n_out > 0) hipLaunchKernelGGL(pinn_resample_draw_kernel, dim3(draw_blocks), dim3(PINN_RESAMPLE_BLOCK), 0, (hipStream_t)stream, A);
-    if (hipGetLastError() != hipSuccess) return fail("resample kernel launch failed");
-#endif
-    return 0;
+    if (fill && (launch("resample kernel", pinn_resample_weights_kernel, nb, PINN_RESAMPLE_BLOCK, smem, stream, A) ||
+                 launch("resample kernel", pinn_resample_offsets_kernel, 1, PINN_RESAMPLE_BLOCK, smem, stream, A)))
+        return 1;
+    return launch("resample kernel", pinn_resample_draw_kernel, draw_blocks, PINN_RESAMPLE_BLOCK, 0, stream, A);       // (n_out > 0 here)
 }
 
 int pinn_resample_points(const float* pool, const float* r, int64_t m, int d, int power, double floor_c, int64_t n_out,
@@ -1648,14 +1624,9 @@ int pinn_port_probe(int which, const void* in, void* out, int n_blocks, void* st
     if (n_blocks < 1 || n_blocks > 1024) return fail("n_blocks=%d outside [1, 1024]", n_blocks);
     const size_t smem = which == PINN_PROBE_LDS_TR16 ? (size_t)PINN_PROBE_LDS_WORDS * 4
                         : (which == PINN_PROBE_WAVE_SYNC || which == PINN_PROBE_FLAGS) ? 4096 : 0;
-#ifdef PINN_EMU
-    (void)stream;
+    int rc = 0;
 #define PINN_PROBE_LAUNCH(kernel, TI, TO) \
-    emu::launch(n_blocks, PINN_PROBE_THREADS, smem, [&] { kernel(static_cast<const TI*>(in), static_cast<TO*>(out)); })
-#else
-#define PINN_PROBE_LAUNCH(kernel, TI, TO) \
-    hipLaunchKernelGGL(kernel, dim3(n_blocks), dim3(PINN_PROBE_THREADS), smem, (hipStream_t)stream, static_cast<const TI*>(in), static_cast<TO*>(out))
-#endif
+    rc = launch("port probe", kernel, n_blocks, PINN_PROBE_THREADS, smem, stream, static_cast<const TI*>(in), static_cast<TO*>(out))
     switch (which) {
         case PINN_PROBE_MFMA16:         PINN_PROBE_LAUNCH(pinn_probe_mfma16, float, float); break;
         case PINN_PROBE_MFMA16_BF16:    PINN_PROBE_LAUNCH(pinn_probe_mfma16_bf16, unsigned, float); break;
@@ -1675,10 +1646,7 @@ int pinn_port_probe(int which, const void* in, void* out, int n_blocks, void* st
         default:                        PINN_PROBE_LAUNCH(pinn_probe_rcp, float, float); break;
     }
 #undef PINN_PROBE_LAUNCH
-#ifndef PINN_EMU
-    if (hipGetLastError() != hipSuccess) return fail("port probe %d: kernel launch failed", which);
-#endif
-    return 0;
+    return rc ? fail("port probe %d: kernel launch failed", which) : 0;
 }
 
 }  // extern "C"

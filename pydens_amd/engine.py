@@ -274,6 +274,17 @@ def _check(t, name, dtype=torch.float32):
         raise ValueError(f'{name} must be a contiguous {dtype} tensor')
 
 
+def _rule(lr, betas, eps, optim):
+    """ the update-rule arguments of an entry point: plain Adam's four numbers, or the `Optim` of the pinn_optim_t family """
+    return (float(lr), float(betas[0]), float(betas[1]), float(eps)) if optim is None else (ctypes.byref(optim), )
+
+
+# Net.fit_steps: (has lr_steps, has optim, has ctrl) -> exported symbol (a schedule always carries an Optim: plain Adam becomes OPT_ADAM)
+_FIT_STEPS = {(False, False, False): 'pinn_fit_steps', (False, False, True): 'pinn_fit_steps_graph',
+              (False, True, False): 'pinn_fit_steps_optim', (False, True, True): 'pinn_fit_steps_optim_graph',
+              (True, True, False): 'pinn_fit_steps_optim_sched', (True, True, True): 'pinn_fit_steps_optim_sched'}
+
+
 class Net:
     """ pinn_t handle + its flat padded parameter layout. """
     def __init__(self, layer_dims, activation, ndims, nparams=0, has_bc=False, bc_value=0.0, has_ic=False,
@@ -463,20 +474,12 @@ class Net:
         _check(mask, 'mask', torch.uint8)
         _check(step_tensor, 'step', torch.int32)
         dirs, nd = self._dirs(dir_cols)
-        if optim is not None:
-            with _on_device(params):
-                self._raise(self.lib.pinn_residual_optim_step(
-                    self.handle, ctypes.byref(residual), _ptr(params), _ptr(xs), xs.shape[0], dirs, nd, n2, _ptr(ic_streams),
-                    float(ic_const), _ptr(grads), _ptr(exp_avg), _ptr(exp_avg_sq), _ptr(mask), _ptr(step_tensor), int(step),
-                    ctypes.byref(optim), None if loss_out is None else ctypes.c_void_p(loss_out), _ptr(workspace),
-                    workspace.numel() * workspace.element_size(), _stream(xs) if stream is None else stream))
-            return
+        fn = self.lib.pinn_residual_adam_step if optim is None else self.lib.pinn_residual_optim_step
         with _on_device(params):
-            self._raise(self.lib.pinn_residual_adam_step(
+            self._raise(fn(
                 self.handle, ctypes.byref(residual), _ptr(params), _ptr(xs), xs.shape[0], dirs, nd, n2, _ptr(ic_streams),
                 float(ic_const), _ptr(grads), _ptr(exp_avg), _ptr(exp_avg_sq), _ptr(mask), _ptr(step_tensor), int(step),
-                float(lr), float(betas[0]), float(betas[1]), float(eps),
-                None if loss_out is None else ctypes.c_void_p(loss_out), _ptr(workspace),
+                *_rule(lr, betas, eps, optim), None if loss_out is None else ctypes.c_void_p(loss_out), _ptr(workspace),
                 workspace.numel() * workspace.element_size(), _stream(xs) if stream is None else stream))
 
     def fit_steps(self, residual, params, xs, columns, seed, call_index0, grads, workspace, exp_avg, exp_avg_sq, mask,
@@ -506,28 +509,19 @@ class Net:
             rates = (ctypes.c_float * max(1, k_steps))(*[float(v) for v in lr_steps])
             if optim is None:       # (plain Adam as a rule of the family: the same arithmetic, include/pinn.h pinn_optim_t)
                 optim = Optim.build(OPT_ADAM, lr, betas=betas, eps=eps)
-        rule = (float(lr), float(betas[0]), float(betas[1]), float(eps)) if optim is None else (ctypes.byref(optim), )
-        common = (self.handle, ctypes.byref(residual), _ptr(params), _ptr(xs), xs.shape[0], kind, a, b,
-                  int(seed) & (2 ** 64 - 1), int(call_index0), dirs, nd, n2, float(ic_const), _ptr(grads), _ptr(exp_avg),
-                  _ptr(exp_avg_sq), _ptr(mask), _ptr(step_tensor), int(step0), *rule,
-                  _ptr(loss_history), int(k_steps), _ptr(workspace), workspace.numel() * workspace.element_size())
+        args = (self.handle, ctypes.byref(residual), _ptr(params), _ptr(xs), xs.shape[0], kind, a, b,
+                int(seed) & (2 ** 64 - 1), int(call_index0), dirs, nd, n2, float(ic_const), _ptr(grads), _ptr(exp_avg),
+                _ptr(exp_avg_sq), _ptr(mask), _ptr(step_tensor), int(step0), *_rule(lr, betas, eps, optim),
+                _ptr(loss_history), int(k_steps), _ptr(workspace), workspace.numel() * workspace.element_size())
+        # `ctrl`: a uint8 device tensor of pinn_fit_ctrl_bytes() bytes -- the chunk as one replayable launch graph (the library falls
+        # back to the eager loop by itself where a graph does not apply); the schedule's entry point takes one always, NULL included
+        if ctrl is not None or rates is not None:
+            args += (_ptr(ctrl), 0 if ctrl is None else ctrl.numel() * ctrl.element_size())
+        args += (_stream(xs) if stream is None else stream, )
+        if rates is not None:
+            args += (rates, )
         with _on_device(params):
-            if rates is not None:
-                self._raise(self.lib.pinn_fit_steps_optim_sched(*common, _ptr(ctrl), 0 if ctrl is None else ctrl.numel() * ctrl.element_size(),
-                                                                _stream(xs) if stream is None else stream, rates))
-            elif optim is not None:
-                if ctrl is not None:
-                    self._raise(self.lib.pinn_fit_steps_optim_graph(*common, _ptr(ctrl), ctrl.numel() * ctrl.element_size(),
-                                                                    _stream(xs) if stream is None else stream))
-                else:
-                    self._raise(self.lib.pinn_fit_steps_optim(*common, _stream(xs) if stream is None else stream))
-            elif ctrl is not None:
-                # `ctrl`: a uint8 device tensor of pinn_fit_ctrl_bytes() bytes -- the chunk as one replayable launch graph
-                # (pinn_fit_steps_graph; the library falls back to the eager loop by itself where a graph does not apply)
-                self._raise(self.lib.pinn_fit_steps_graph(*common, _ptr(ctrl), ctrl.numel() * ctrl.element_size(),
-                                                          _stream(xs) if stream is None else stream))
-            else:
-                self._raise(self.lib.pinn_fit_steps(*common, _stream(xs) if stream is None else stream))
+            self._raise(getattr(self.lib, _FIT_STEPS[rates is not None, optim is not None, ctrl is not None])(*args))
 
     def sample_points(self, xs, columns, seed, call_index, stream=None):
         """ fill xs [N, d] on the device: columns = [(kind, a, b), ...] with kind SAMPLE_UNIFORM (a + (b - a) u),
@@ -544,42 +538,28 @@ class Net:
                                                     int(call_index), _stream(xs) if stream is None else stream))
         return xs
 
+    def _update_step(self, name, rule, params, grads, exp_avg, exp_avg_sq, mask, step, at, loss_out, stream):
+        for t, what in ((params, 'params'), (grads, 'grads'), (exp_avg, 'exp_avg'), (exp_avg_sq, 'exp_avg_sq')):
+            _check(t, what)
+        _check(mask, 'mask', torch.uint8)
+        _check(step, 'step', torch.int32)
+        head = (_ptr(params), _ptr(grads), _ptr(exp_avg), _ptr(exp_avg_sq), _ptr(mask), params.numel(), _ptr(step))
+        with _on_device(params):
+            if at > 0:
+                self._raise(getattr(self.lib, name + '_at')(*head, int(at), *rule, None if loss_out is None else ctypes.c_void_p(loss_out),
+                                                            int(self.layout.off_loss), _stream(params) if stream is None else stream))
+            else:
+                self._raise(getattr(self.lib, name)(*head, *rule, _stream(params)))
+
     def adam_step(self, params, grads, exp_avg, exp_avg_sq, mask, step, lr, betas=(0.9, 0.999), eps=1e-8, at=0,
                   loss_out=None, stream=None):
         """ `step`: int32 device counter; at > 0: the host's 1-based step count (one launch, counter mirrored);
         loss_out: device ADDRESS (int) that receives grads[off_loss] in the same launch (at > 0 only) """
-        for t, name in ((params, 'params'), (grads, 'grads'), (exp_avg, 'exp_avg'), (exp_avg_sq, 'exp_avg_sq')):
-            _check(t, name)
-        _check(mask, 'mask', torch.uint8)
-        _check(step, 'step', torch.int32)
-        if at > 0:
-            with _on_device(params):
-                self._raise(self.lib.pinn_adam_step_at(_ptr(params), _ptr(grads), _ptr(exp_avg), _ptr(exp_avg_sq), _ptr(mask),
-                                                       params.numel(), _ptr(step), int(at), float(lr), float(betas[0]),
-                                                       float(betas[1]), float(eps),
-                                                       None if loss_out is None else ctypes.c_void_p(loss_out),
-                                                       int(self.layout.off_loss), _stream(params) if stream is None else stream))
-            return
-        with _on_device(params):
-            self._raise(self.lib.pinn_adam_step(_ptr(params), _ptr(grads), _ptr(exp_avg), _ptr(exp_avg_sq), _ptr(mask),
-                                                params.numel(), _ptr(step), float(lr), float(betas[0]), float(betas[1]),
-                                                float(eps), _stream(params)))
+        self._update_step('pinn_adam_step', _rule(lr, betas, eps, None), params, grads, exp_avg, exp_avg_sq, mask, step, at, loss_out, stream)
 
     def optim_step(self, params, grads, exp_avg, exp_avg_sq, mask, step, optim, at=0, loss_out=None, stream=None):
         """ `adam_step` with the update rule of `optim` (an `Optim`; include/pinn.h pinn_optim_step / pinn_optim_step_at) """
-        for t, name in ((params, 'params'), (grads, 'grads'), (exp_avg, 'exp_avg'), (exp_avg_sq, 'exp_avg_sq')):
-            _check(t, name)
-        _check(mask, 'mask', torch.uint8)
-        _check(step, 'step', torch.int32)
-        with _on_device(params):
-            if at > 0:
-                self._raise(self.lib.pinn_optim_step_at(_ptr(params), _ptr(grads), _ptr(exp_avg), _ptr(exp_avg_sq), _ptr(mask),
-                                                        params.numel(), _ptr(step), int(at), ctypes.byref(optim),
-                                                        None if loss_out is None else ctypes.c_void_p(loss_out),
-                                                        int(self.layout.off_loss), _stream(params) if stream is None else stream))
-            else:
-                self._raise(self.lib.pinn_optim_step(_ptr(params), _ptr(grads), _ptr(exp_avg), _ptr(exp_avg_sq), _ptr(mask),
-                                                     params.numel(), _ptr(step), ctypes.byref(optim), _stream(params)))
+        self._update_step('pinn_optim_step', _rule(None, None, None, optim), params, grads, exp_avg, exp_avg_sq, mask, step, at, loss_out, stream)
 
     # ---- L-BFGS (include/pinn.h pinn_lbfgs_direction) --------------------------------------------------------------------------------
     def lbfgs_ctrl_doubles(self, history):
