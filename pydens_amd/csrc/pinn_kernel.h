@@ -1314,9 +1314,11 @@ template <bool NT> PINN_DEVICE f32x4 pinn_ld4_stream(const f32x4* p) {
 }
 PINN_DEVICE void pinn_st4(float* p, f32x4 v) { *reinterpret_cast<f32x4*>(p) = v; }
 // ---- split-bf16 operands -----------------------------------------------------------------------------------------------
-// x = hi + mid + lo EXACTLY, each a bf16: hi = x truncated to its upper 16 bits, mid = (x - hi) truncated, lo = x - hi - mid
-// (the subtractions are exact: 24 = 8 + 8 + 8 mantissa bits). Four VALU operations per value, then one v_perm_b32 per PAIR of
-// values and plane packs the upper halves (the pack is the truncation of mid and lo).
+// x = hi + mid + lo EXACTLY, each a bf16: hi = x rounded to nearest at its upper 16 bits, mid = (x - hi) rounded likewise,
+// lo = x - hi - mid (the subtractions are exact: 24 = 8 + 8 + 8 mantissa bits, and rounding only shortens the remainders).
+// Six VALU operations per value (PINN_SP_ROUND 2; four with truncation, PINN_SP_ROUND 0), then one v_perm_b32 per PAIR of
+// values and plane packs the upper halves (the pack takes the upper 16 bits of the -- already rounded -- hi and mid patterns,
+// and of lo, which has no bits below them).
 PINN_DEVICE unsigned pinn_fbits(float x) { return __builtin_bit_cast(unsigned, x); }
 PINN_DEVICE float pinn_bitsf(unsigned x) { return __builtin_bit_cast(float, x); }
 // hi and mid are ROUNDED to nearest (+0x8000 on the bit pattern before the mask), lo takes the rest exactly. Truncation would be
@@ -1327,7 +1329,9 @@ PINN_DEVICE float pinn_bitsf(unsigned x) { return __builtin_bit_cast(float, x); 
 #ifndef PINN_SP_ROUND
 #define PINN_SP_ROUND 2         // 0: hi and mid by truncation; 1: mid rounded to nearest; 2: hi and mid rounded
 #endif
+#ifndef PINN_SP_NPROD
 #define PINN_SP_NPROD 6         // partial products per GEMM step: those with i + j <= 2 (all nine bought no accuracy: section 6b)
+#endif                          // (5 / 3: the deliberately wrong builds of tests/test_split_bf16.py -- a dropped lo x hi product, no i + j = 2 product)
 // bit patterns whose UPPER halves are the three bf16 parts of x (b0: hi, b1: mid, b2: lo); x = hi + mid + lo exactly
 PINN_DEVICE void pinn_split3(float x, unsigned& b0, unsigned& b1, unsigned& b2) {
     if (PINN_ABL & 1) { b0 = b1 = b2 = pinn_fbits(x); return; }
@@ -2000,8 +2004,11 @@ PINN_DEVICE void pinn_tile_body(const PinnKArgs& A, const float* params_, float*
         pinn_s16x8 wsf[SPK][3];       // split-bf16: forward weight fragments of the NEXT hidden layer, one phase ahead
         if constexpr (SPLIT) {
             sp_weights(0, 0, wsf);
+            // (no hidden->hidden layer, lh == 0: there is no bias behind off_wh + HP * HP -- the parameter buffer ends before it. The load
+            //  then reads the first floats of the buffer, which nobody uses; one scalar select, the same loads otherwise)
+            const size_t bias0 = lh > 0 ? (size_t)A.off_wh + (size_t)HP * HP : 0;
 #pragma unroll
-            for (int j = 0; j < NTW; ++j) biasn[j] = pinn_ld4(params_ + A.off_wh + HP * HP + unit0(j));
+            for (int j = 0; j < NTW; ++j) biasn[j] = pinn_ld4(params_ + bias0 + unit0(j));
         }
         f32x4 hskip[SKIPS ? NTW : 1][SKIPS ? MT : 1][S];      // activations carried by the open skip connection
         const PinnAct act0 = act_at(0);

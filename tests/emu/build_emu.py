@@ -78,12 +78,15 @@ def _build(force, extra_flags, tag, widths):
     if split_here:
         jobs += [[CXX, *FLAGS, *extra_flags, '-DPINN_INST_HP=64', f'-DPINN_INST_SPLIT={n}', '-c', os.path.join(CSRC, 'pinn_inst.inc'),
                   '-o', os.path.join(tbuild, f'inst_hp64_split{n}.o')] for n in (1, 2)]
+    wide_split = [hp for hp in (128, 256) if hp in widths]       # ... and the wide split units (tile + weight-gradient kernel) to theirs
+    jobs += [[CXX, *FLAGS, *extra_flags, f'-DPINN_INST_HP={hp}', '-DPINN_INST_SPLIT=1', '-c', os.path.join(CSRC, 'pinn_inst.inc'),
+              '-o', os.path.join(tbuild, f'inst_hp{hp}_split.o')] for hp in wide_split]
     with ThreadPoolExecutor(max_workers=os.cpu_count() or 4) as pool:
         objs = list(pool.map(_run, jobs))
     objs += [os.path.join(BUILD, f'inst_hp{hp}.o') for hp in WIDTHS if hp not in widths]
     if not split_here:
         objs += [os.path.join(BUILD, f'inst_hp64_split{n}.o') for n in (1, 2)]
-    objs += [os.path.join(BUILD, f'inst_hp{hp}_split.o') for hp in (128, 256)]
+    objs += [os.path.join(BUILD, f'inst_hp{hp}_split.o') for hp in (128, 256) if hp not in wide_split]
     objs.append(os.path.join(BUILD, 'inst_hp64_own1.o'))
     objs += [os.path.join(BUILD, f'inst_hp{hp}_allact{part}.o') for hp in ALLACT_WIDTHS for part in ((1, 2) if hp >= 128 else (1,))]   # (second set of full breadth kernels: the default build's)
     objs += [os.path.join(BUILD, 'abi.o'), os.path.join(BUILD, 'emu_runtime.o')]
