@@ -955,7 +955,10 @@ static int run_train(pinn_t* net, PinnKArgs* a, const Plan& plan, int nd, float*
         long long has[3] = {0, 0, 0};
         const size_t pc = (size_t)net->lay.p_total;
         bool ok = !plan.wgx && !plan.wt_global && !plan.split && plan.chunk_tiles >= plan.ntiles && !g_profile &&
-                  (!aux_bytes || net->prepass_in_kernel) && plan.fn(nd, plan.n2k, a, plan.grid, stream, 3, has) == 0 && has[0];
+                  (!aux_bytes || a->pre.n_ops > 0) && plan.fn(nd, plan.n2k, a, plan.grid, stream, 3, has) == 0 && has[0];
+        // (pre-pass rows: only where the pre-pass went INTO the kernel above, which then evaluates it for every batch it draws. One that
+        //  took the separate pinn_aux_kernel launch -- switched off, or more double registers than prepass_floats_per_lane holds -- wrote
+        //  the rows of the batch in `xs` once: the chunk keeps the launch graphs or the eager loop, which run it every iteration)
         const int vw = (int)has[1];
         const bool onecu = ok && net->fit_persistent == 2 && vw >= 2 && vw <= 8 && plan.ntiles <= (int64_t)vw * net->fit_onecu_rounds;
         const bool gridform = ok && net->fit_persistent == 1 && plan.grid <= PINN_FIT_MAX_WGS;
@@ -981,6 +984,14 @@ static int run_train(pinn_t* net, PinnKArgs* a, const Plan& plan, int nd, float*
             if (rc == 1) return 0;               // (this instantiation has no such form after all: the caller falls back)
             if (rc) return fail("fit kernel launch failed (%d)", rc);
             tail->persist->launched = true;
+            if (onecu) {
+                // pinn_last_launch_info: ONE workgroup of vw virtual ones, and the LDS it asked for (PinnFitVw: the blocks and W^T of
+                // query 3, then state, rows, batch and pre-pass rows as in resident_floats)
+                const long long pcp = ((long long)pc + 3) / 4 * 4, n = a->n_points;
+                const long long resident = (3 + vw) * pcp + (n * a->d + 3) / 4 * 4 + (n * a->n_aux + 3) / 4 * 4;
+                g_pinn_last_launch[0] = 1; g_pinn_last_launch[1] = 1;
+                g_pinn_last_launch[2] = plan.threads * vw; g_pinn_last_launch[3] = (int)(has[2] + 4 * resident);
+            }
             g_fit_last_sync = onecu ? nullptr : P.sync;        // (grid form: its timeout flag, read back by pinn_fit_chunk_status)
         }
         return 0;
