@@ -466,7 +466,7 @@ class Solver:
                                       'forward() may wrap torch code around self.conv_block(xs)) are backed by the HIP kernels')
         self.custom_forward = self.model.custom_forward
         self._imap = UNSET                                                # custom forward(): _input_map of the running step
-        self._map_pattern, self._map_affine = None, False                 # ... and what _check_input_map found at construction
+        self._map_pattern, self._map_affine, self._map_scale = None, False, None       # ... and what _check_input_map found at construction
         current_model.set(self.model)                                     # :316-317
         self.ctx = copy_context()
         self.device = self.model.flat.device
@@ -485,13 +485,13 @@ class Solver:
         # constraint terms (:451-457) the tracer can lower run as further residual programs over the value stream on
         # their own few points; the others keep the generic path (entry None, reason in constraint_errors)
         self.constraint_plans, self.constraint_errors = [], []
+        self.constraint_specs = []           # per constraint: one StreamSpec per model call it makes (_discover_constraint)
+        self.constraint_dry_run_errors = []  # ... or why that dry run failed (None: it did not)
         self._born_in_constraint = {}        # constraint number -> variables first created by tracing it (dormant until
         self._constraints_seen = set()       # a fit call has evaluated that constraint: reference :420 vs :457)
         for num, constraint in enumerate(self.constraints):
             before = set(self.model.variables)
-            plan, err = self._try_compile_constraint(constraint)
-            self.constraint_plans.append(plan)
-            self.constraint_errors.append(err)
+            self._compile_constraint(num, constraint)
             self._born_in_constraint[num] = set(self.model.variables) - before
             self.model.dormant_variables |= self._born_in_constraint[num]
         self._traced_constraints = tuple(self.constraints)
@@ -606,7 +606,7 @@ class Solver:
             raise NotImplementedError('a custom forward() must call self.conv_block on a tensor of points')
         return ys
 
-    def _input_map(self, pts, inside=False):
+    def _input_map(self, pts, inside=False, known_scale=False):
         """ custom forward(): what does it hand to `self.conv_block`? Asked in every step (a probe call of the forward()).
           None               the batch itself;
           (ys, scale, None)  a fixed per-column affine map `ys[:, k] = a_k * pts[:, k] + b_k` (input normalisation, `2 * xs - 1`): the kernels
@@ -617,7 +617,9 @@ class Solver:
                              (trace.StreamContext._through_map; pattern[k][c] = "ys_k depends on column c", found at construction).
         What the reference's seam (model_torch.py:52-54) also takes and this does not: a map that depends on trainable parameters (its
         gradient would need the streams' own derivatives), on the batch as a whole, or that changes the number of columns (the reference
-        builds `conv_block` for `total` inputs, :167): NotImplementedError. """
+        builds `conv_block` for `total` inputs, :167): NotImplementedError.
+        known_scale: the few points of a constraint's own model call, where a column often holds ONE value (`t0 = zeros`, a face `x = 1`):
+        such a column takes the scale the construction found on its 64 random points; a batch of the equation is refused instead. """
         pts = pts.detach()
         ys = self._conv_block_argument(pts, inside)
         if (ys.data_ptr() == pts.data_ptr() and ys.shape == pts.shape and ys.stride() == pts.stride() and ys.dtype == pts.dtype
@@ -637,9 +639,15 @@ class Solver:
         lo, hi = x64.argmin(dim=0), x64.argmax(dim=0)
         k = torch.arange(x64.shape[1], device=x64.device)
         span = x64[hi, k] - x64[lo, k]
-        flat = span <= 0                                    # a column without two different values: only the identity is recognisable
-        a = torch.where(flat, torch.ones_like(span), (y64[hi, k] - y64[lo, k]) / torch.where(flat, torch.ones_like(span), span))
-        b = torch.where(flat, torch.zeros_like(span), y64[lo, k] - a * x64[lo, k])     # (such a column must come through unchanged)
+        flat = span <= 0                                    # a column without two different values: only the identity is recognisable,
+        known = torch.ones_like(span)                       # or the scale the construction found (a constraint's points: `t0 = zeros`)
+        known_scale = known_scale and self._map_affine and self._map_scale is not None
+        if known_scale:
+            known = torch.tensor(self._map_scale, dtype=torch.float64, device=x64.device)
+        a = torch.where(flat, known, (y64[hi, k] - y64[lo, k]) / torch.where(flat, torch.ones_like(span), span))
+        b = y64[lo, k] - a * x64[lo, k]                     # (a flat column of an unknown map must come through unchanged: a = 1, b = 0)
+        if not known_scale:
+            b = torch.where(flat, torch.zeros_like(span), b)
         # (fp32 arithmetic of the user's map: a few ulp of its largest intermediate)
         err = (y64 - (a * x64 + b)).abs() - 1e-5 * ((a * x64).abs() + b.abs() + y64.abs())
         if float(err.max()) <= 0.0:
@@ -654,12 +662,13 @@ class Solver:
         fit call), is it a map of each point by itself, and -- if it is not per-column affine -- which input column of the network depends
         on which column of the solver. """
         total = self.model.total
-        self._map_pattern, self._map_affine = None, False
+        self._map_pattern, self._map_affine, self._map_scale = None, False, None
         pts = torch.rand((64, total), device=self.device)
         imap = self._input_map(pts)
         if imap is None:
             return
         self._map_affine = imap[1] is not None
+        self._map_scale = imap[1]
         part = self._input_map(pts[:23].contiguous())
         if part is None or not torch.allclose(part[0], imap[0][:23], rtol=1e-6, atol=1e-7):
             raise NotImplementedError('a custom forward() may call self.conv_block only on a map of each point by itself (this one depends on '
@@ -741,11 +750,7 @@ class Solver:
                     continue
                 known = num < len(self._traced_constraints) and constraint is self._traced_constraints[num]
                 before = set(self.model.variables)
-                plan, err = self._try_compile_constraint(constraint)
-                if num < len(self.constraint_plans):
-                    self.constraint_plans[num], self.constraint_errors[num] = plan, err
-                else:
-                    self.constraint_plans.append(plan); self.constraint_errors.append(err)
+                self._compile_constraint(num, constraint)
                 if not known:
                     # a constraint appended after construction: variables its tracing brings to life are dormant until a fit
                     # call has evaluated it, exactly as for the constraints __init__ saw (reference :420 vs :457)
@@ -857,29 +862,54 @@ class Solver:
             root, pts = trace.symbolic_constraint(
                 constraint, self.ctx.run, total,
                 lambda args: self.reshape_and_concat(args).numpy(), variable_slot=self._variable_slot)
-            spec0 = trace.StreamSpec(set())
-            plan = trace.lower_residual(root, spec0, total)
-            # validation: the program (fp64 host interpreter) vs the callable fed with a stand-in for the model's values
-            values = torch.rand((pts.shape[0], 1), device=self.device) * 2 - 1
-            cols = [torch.from_numpy(pts[:, c:c + 1].copy()).to(self.device) for c in range(total)]
+            lay = model.net.layout
+            # the streams the constraint's `D` asks of its one model call (none: a value constraint, as ever)
             try:
-                want = self.ctx.run(constraint, lambda *args: values, *cols)
-            except (TypeError, ValueError, AttributeError, RuntimeError, LookupError) as err:
+                spec = trace.StreamSpec(trace.requested_streams(root), hp=lay.hp, allact=model.net.allact)
+            except NotImplementedError as err:      # (what the kernels do not carry at this width: the fit call that uses the term raises it)
+                raise trace.TraceUnsupported(str(err)) from err
+            # one call record per constraint: what one call of the constraint kernels cannot serve keeps the generic path
+            if spec.n3 > 0 or spec.n4 > 0:
+                raise trace.TraceUnsupported(f'{spec}: third- and fourth-order derivatives in a constraint run on the generic path')
+            if not spec.single_call:
+                raise trace.TraceUnsupported(f'{spec} needs several kernel calls (more than one direction group: generic path)')
+            plan = trace.lower_residual(root, spec, total)
+            # validation: the program (fp64 host interpreter) vs the callable fed with stand-ins for the model's value and every stream
+            n_c = pts.shape[0]
+            values = torch.rand((n_c, 1), device=self.device) * 2 - 1
+            streams = values.reshape(1, -1)
+            if spec.n_streams > 1:
+                streams = torch.cat([streams, torch.rand((spec.n_streams - 1, n_c), device=self.device) * 2 - 1], dim=0)
+            cols = [torch.from_numpy(pts[:, c:c + 1].copy()).to(self.device) for c in range(total)]
+
+            def stand_in(*args):
+                if spec.nd == 0:
+                    return values
+                sc = self._tag_streams(trace.StreamContext(total).bind_args(args), spec, streams)       # (`D` resolves to the stand-in streams)
+                trace.active_streams.set(sc)
+                return sc.tensors[()]
+            try:
+                want = self.ctx.run(trace.call_constraint, constraint, stand_in, *cols)
+            except (TypeError, ValueError, AttributeError, RuntimeError, LookupError, NotImplementedError) as err:
                 raise trace.TraceUnsupported(f'{type(err).__name__}: {err}') from err
             want = torch.as_tensor(want).detach().reshape(-1).double().cpu().numpy()
-            lay = model.net.layout
             var_values = model.flat[lay.off_extra:lay.off_extra + plan.n_vars].detach().cpu().numpy()
-            got = trace.run_residual_numpy(plan, values.cpu().numpy().reshape(1, -1), pts, var_values)
+            got = trace.run_residual_numpy(plan, streams.cpu().numpy(), pts, var_values)
             if got.shape != want.shape or not np.allclose(got, want, rtol=1e-4, atol=1e-5):
                 raise trace.TraceUnsupported('traced constraint disagrees with the callable')
         except trace.TraceUnsupported as err:
             return None, str(err)
         points = torch.from_numpy(pts).to(self.device).contiguous()
+        # the callable initial condition at the constraint's points, one row per stream: computed once, the points are constants
         ic = None
         if model.initial_condition is not None and model.ic_constant is None and self.ic_var_slot is None:
-            with torch.no_grad():
-                ic = self.ctx.run(model.ic_values, points).expand(points.shape[0], 1).reshape(1, -1).float().contiguous()
-        return dict(program=self._with_ic_variable(plan.to_struct()), plan=plan, points=points, ic=ic), None
+            if spec.nd == 0:
+                with torch.no_grad():
+                    ic = self.ctx.run(model.ic_values, points).expand(points.shape[0], 1).reshape(1, -1).float().contiguous()
+            else:
+                ic = self._ic_stream_tensor(points, None, spec).contiguous()
+        return dict(program=self._with_ic_variable(plan.to_struct()), plan=plan, points=points, ic=ic, spec=spec,
+                    dir_cols=list(spec.dir_cols), n2p=spec.n2p), None
 
     def _with_ic_variable(self, residual):
         residual.ic_var1 = 0 if self.ic_var_slot is None else self.ic_var_slot + 1
@@ -890,7 +920,10 @@ class Solver:
         added to / stored in `self.grads`; every data-parallel rank evaluates it, hence the 1 / world in front of the all-reduce. """
         cp, model = self.constraint_plans[num], self.model
         n_c = 1 if self._crit_sum else cp['points'].shape[0]            # (reduction='sum': no division by the number of points)
-        model.net.residual_step(cp['program'], model.flat, cp['points'], self.grads, model.workspace(n_c, 0, 0), (), 0,
+        # (a constraint that differentiates the model carries the directions of its streams: one launch of that instantiation)
+        spec = cp['spec']
+        ws = model.workspace(n_c, 0, 0) if spec.nd == 0 else model.workspace(cp['points'].shape[0], spec.nd, cp['n2p'])
+        model.net.residual_step(cp['program'], model.flat, cp['points'], self.grads, ws, cp['dir_cols'], cp['n2p'],
                                 ic_streams=cp['ic'], ic_const=model.kernel_ic_const(),
                                 inv_n_global=1.0 / (n_c * world), accumulate=accumulate)
 
@@ -904,20 +937,18 @@ class Solver:
                 return off - lay.off_extra
         return None
 
-    def _eval_equation(self, streams, xs, ic_streams=None, requires_grad=True):
-        """ run the user's callable on stream tensors [S,N] (+ optional IC streams), D resolves to streams. """
-        total = self.model.total
-        sc = trace.StreamContext(total)
-        imap = self._imap if self.custom_forward else None
-        scale = None if imap is None or imap is UNSET or imap[1] is None or all(a == 1.0 for a in imap[1]) else imap[1]
-
+    @staticmethod
+    def _tag_streams(sc, spec, streams, ic_streams=None, scale=None):
+        """ the kernel streams of `spec` ([S, N], or a list of rows) as tagged [N, 1] tensors of the stream context `sc`, the
+        user-visible mixed partials combined from their diagonals: what `D` picks from. For the equation on the batch and for every
+        model call of a constraint alike. """
         def tag(t, alpha):
             # streams taken at an affine map of the points (custom forward(), _input_map): chain rule back to the solver's columns
             if scale is not None and alpha:
                 t = t * math.prod(scale[c] for c in alpha)
             return sc.tag(t, alpha)
         full = {}
-        for alpha, idx in self.spec.index.items():
+        for alpha, idx in spec.index.items():
             t = streams[idx].view(-1, 1)
             if ic_streams is not None and ic_streams[idx] is not None:
                 t = t + ic_streams[idx]
@@ -927,15 +958,54 @@ class Solver:
                 #  expression asks autograd for the partial derivative with respect to every tagged stream, and a mixed partial that hung
                 #  below the tagged u_aa would be counted in d / d u_aa a second time)
                 tag(t.view_as(t), alpha)
-        for ab, (ivv, iaa, ibb) in self.spec.mixed.items():      # u_ab = (u_vv - u_aa - u_bb) / 2
+        for ab, (ivv, iaa, ibb) in spec.mixed.items():      # u_ab = (u_vv - u_aa - u_bb) / 2
             tag(0.5 * (full[ivv] - full[iaa] - full[ibb]), ab)
-        for alpha, (ip, im, ia, ib) in self.spec.mixed4.items():         # u_aabb = (D4_{a+b} + D4_{a-b} - 2 u_aaaa - 2 u_bbbb) / 12
+        for alpha, (ip, im, ia, ib) in spec.mixed4.items():         # u_aabb = (D4_{a+b} + D4_{a-b} - 2 u_aaaa - 2 u_bbbb) / 12
             tag((full[ip] + full[im] - 2.0 * full[ia] - 2.0 * full[ib]) / 12.0, alpha)
-        for alpha, terms in list(self.spec.mixed31.items()) + list(self.spec.mixed111.items()):
+        for alpha, terms in list(spec.mixed31.items()) + list(spec.mixed111.items()):
             # u_aaab / u_abbb from D4 along a +- b and 2a +- b; u_abc from D3 along a +- b +- c (round 6)
             tag(sum(coef * full[idx] for idx, coef in terms), alpha)
-        for alpha, (ip, im, i3, sign) in self.spec.mixed3.items():      # u_aab = (D3_{a+b} - D3_{a-b} - 2 u_bbb) / 6, u_abb: + D3_{a-b}, - 2 u_aaa
+        for alpha, (ip, im, i3, sign) in spec.mixed3.items():      # u_aab = (D3_{a+b} - D3_{a-b} - 2 u_bbb) / 6, u_abb: + D3_{a-b}, - 2 u_aaa
             tag((full[ip] + sign * full[im] - 2.0 * full[i3]) / 6.0, alpha)
+        return sc
+
+    def _streams_forward(self, kpts, spec, slot=0):
+        """ the streams of `spec` at the points `kpts` [S, N] (no autograd): one pinn_jet_forward, or one per direction group.
+        slot: which call of the step this is (the equation: 0) -- the cached row indices of the groups are kept per call """
+        model = self.model
+        if len(spec.groups) == 1:
+            return model.net.jet_forward(model.flat, kpts, spec.dir_cols, spec.n2p, ic_const=model.kernel_ic_const())
+        # more directions than one kernel call carries: one forward per group of directions (u comes with each)
+        leaf = torch.empty((spec.n_streams, kpts.shape[0]), dtype=torch.float32, device=self.device)
+        for num, (dirs_g, n2g, idx) in enumerate(spec.groups):
+            part = model.net.jet_forward(model.flat, kpts, dirs_g, n2g, ic_const=model.kernel_ic_const())
+            leaf.index_copy_(0, self._group_rows((slot, num), idx), part)
+        return leaf
+
+    def _streams_backward(self, kpts, spec, grad, slot=0):
+        """ upstream gradients of the streams [S, N] -> parameter gradients, ADDED to `self.grads` (pinn_jet_backward, per group) """
+        model = self.model
+        if len(spec.groups) == 1:
+            ws = model.workspace(kpts.shape[0], spec.nd, spec.n2p)
+            model.net.jet_backward(model.flat, kpts, grad.contiguous(), self.grads, ws, spec.dir_cols, spec.n2p,
+                                   ic_const=model.kernel_ic_const(), accumulate=True)
+            return
+        # the parameter gradient is linear in the upstream stream gradients: one backward per group, the
+        # gradient of u itself rides with the first group only
+        for num, (dirs_g, n2g, idx) in enumerate(spec.groups):
+            gin = grad.index_select(0, self._group_rows((slot, num), idx))
+            if num > 0:
+                gin[0].zero_()
+            ws = model.workspace(kpts.shape[0], len(dirs_g), n2g)
+            model.net.jet_backward(model.flat, kpts, gin, self.grads, ws, dirs_g, n2g,
+                                   ic_const=model.kernel_ic_const(), accumulate=True)
+
+    def _eval_equation(self, streams, xs, ic_streams=None, requires_grad=True):
+        """ run the user's callable on stream tensors [S,N] (+ optional IC streams), D resolves to streams. """
+        total = self.model.total
+        imap = self._imap if self.custom_forward else None
+        scale = None if imap is None or imap is UNSET or imap[1] is None or all(a == 1.0 for a in imap[1]) else imap[1]
+        sc = self._tag_streams(trace.StreamContext(total), self.spec, streams, ic_streams, scale)
         cols = []
         for c in range(total):
             col = xs[:, c:c + 1]
@@ -945,9 +1015,14 @@ class Solver:
             cols.append(col)
         return self.ctx.run(trace.call_with_streams, sc, self._eq, sc.tensors[()], *cols)
 
-    def _ic_streams(self, xs, create_graph):
-        """ IC(x_spatial) and its derivative streams as a list over stream indices ([N,1] tensors or None). """
-        m, spec = self.model, self.spec
+    def _ic_streams(self, xs, create_graph, spec=None):
+        """ IC(x_spatial) and its derivative streams as a list over stream indices ([N,1] tensors or None). spec: the equation's, or
+        that of a constraint's model call. """
+        own_points = spec is not None            # (a constraint's model call: often ONE point, `p = torch.tensor([[1.0]])`)
+        m, spec = self.model, (self.spec if spec is None else spec)
+        if own_points and xs.shape[0] == 1 and m.ic_constant is None:
+            # (a callable IC that returns ONE value is taken for a constant below: a lone point is evaluated as two copies of itself)
+            return [None if t is None else t[:1] for t in self._ic_streams(xs.repeat(2, 1), create_graph, spec)]
         cols = [xs[:, i].clone().requires_grad_() for i in range(m.ndims_spatial)]
         val = self.ctx.run(m.initial_condition, *cols)
         if not isinstance(val, torch.Tensor):
@@ -987,11 +1062,11 @@ class Solver:
             out = [None if t is None else t.detach() for t in out]
         return out
 
-    def _ic_stream_tensor(self, xs, comb_w):
+    def _ic_stream_tensor(self, xs, comb_w, spec=None):
         """ [S_kernel, N] IC streams by torch autograd over the callable (ICs the tracer could not lower) """
-        spec = self.spec
+        spec = self.spec if spec is None else spec
         n2 = spec.n2 if comb_w is None else 1
-        parts = self._ic_streams(xs, create_graph=False)
+        parts = self._ic_streams(xs, create_graph=False, spec=spec)
         ic_streams = torch.zeros((1 + spec.nd + n2 + (spec.n3 if comb_w is None else 0), xs.shape[0]), dtype=torch.float32,
                                  device=self.device)
         for i, t in enumerate(parts):
@@ -1209,10 +1284,14 @@ class Solver:
         """ does the loss of the dry evaluation hold the network's value (and with it the output bias, which the derivatives of the network
         do not hold)? `probe['streams']`: per kernel stream, whether the backward gave it a gradient. Stream 0 is u; the derivative streams
         along direction k hold the value through the product rule where the ansatz factor varies along k. """
-        model, spec = self.model, self.spec
         if probe.get('value') or not probe['streams']:
             return bool(probe.get('value'))
-        streams = probe['streams']
+        return self._streams_reach_value(probe['streams'], self.spec)
+
+    def _streams_reach_value(self, streams, spec):
+        """ `streams`: per kernel stream of `spec`, whether the backward gave it a gradient -- the equation's on the batch, or those of a
+        model call a constraint made at its own points """
+        model = self.model
         if streams[0]:
             return True
         varying = set()
@@ -1688,6 +1767,89 @@ class Solver:
             self._constraint_step(num, world, accumulate=not first)
             first = False
 
+    def _model_at(self, args, spec, calls, probe=None, discover=False):
+        """ `f(*args)` of a constraint (reference :451-454) on the generic step. spec: the streams the constraint's `D` asks of this call,
+        known from the dry run (`_discover_constraint`); None or value only: the value-only forward with its autograd seam, as ever.
+        Otherwise the value comes back TAGGED like the equation's field: a StreamContext of this call's own over the call's points, the
+        kernel streams as its tensors, the arguments remembered by identity -- `D(value, arg)` picks a stream (tokens.D). The call is
+        appended to `calls` (kernel points, spec, the stream leaf, slot): after `loss.backward()` the streams' gradients go back through
+        pinn_jet_backward. A model with its own forward() runs that forward as torch code around the tagged network value.
+        discover: the dry run -- no kernel, random stand-ins, `calls` receives the stream contexts (what was asked of each). """
+        model, total = self.model, self.model.total
+        if not discover and (spec is None or spec.nd == 0):
+            out = model(self._points_on_device(args))
+            if probe is not None and out.requires_grad:
+                out.register_hook(lambda g: probe.__setitem__('value', True))
+            return out
+        sc = trace.StreamContext(total).bind_args(args)
+        sc.discovering = discover
+        imap = None
+        if self.custom_forward:
+            pts = self.reshape_and_concat(args, device=self.device)         # (keeps the autograd link to the arguments: the ansatz is torch code)
+            imap = self._input_map(pts, inside=True, known_scale=True)
+            if imap is not None and imap[1] is None:
+                raise NotImplementedError('a constraint that differentiates a model whose forward() puts a map in front of the network that '
+                                          'is not per-column affine: not built (the equation term follows such a map)')
+            kpts = pts.detach().contiguous() if imap is None else imap[0]
+        else:
+            kpts = pts = self._points_on_device([a.detach() if torch.is_tensor(a) else a for a in args])
+        if discover:
+            sc.tag(torch.rand((kpts.shape[0], 1), device=self.device).requires_grad_(), ())
+            calls.append((sc, ))
+        else:
+            slot = len(calls) + 1
+            rows = leaf = self._streams_forward(kpts, spec, slot).requires_grad_()
+            if probe is not None:
+                rows = [row.detach().requires_grad_() for row in leaf.detach().unbind(0)]
+            ic_streams = None
+            if model.initial_condition is not None and model.ic_constant is None and not self.custom_forward:
+                ic_streams = self._ic_streams(kpts, create_graph=True, spec=spec)
+            scale = None if imap is None or all(a == 1.0 for a in imap[1]) else imap[1]
+            self._tag_streams(sc, spec, rows, ic_streams, scale)
+            calls.append((kpts, spec, rows, slot))
+        trace.active_streams.set(sc)            # (until the constraint returns: trace.call_constraint)
+        if not self.custom_forward:
+            return sc.tensors[()]
+        model.raw_field = (pts, sc.tensors[()], None if imap is None else imap[0])
+        try:
+            return model.forward(pts)
+        finally:
+            model.raw_field = None
+
+    def _discover_constraint(self, constraint):
+        """ dry run of a constraint (as trace.discover is the equation's): one StreamSpec per model call, in call order -- which streams
+        its `D` asks of the model at the constraint's own points. None: the dry run failed for a reason of its own, kept in
+        `constraint_dry_run_errors` (the step then evaluates the model by value, as it always did, and says what is wrong); an exception
+        object: an order or partial the kernels do not carry, raised by the fit call that uses the constraint.
+        -> (specs, why the dry run failed or None) """
+        calls = []
+        lay = self.model.net.layout
+        try:
+            # (stand-in values on a fork of the generators: a later fit samples what it would have sampled without this dry run)
+            with torch.random.fork_rng(devices=[self.device] if self.device.type == 'cuda' else []):
+                cols = [torch.rand((3, 1), device=self.device).requires_grad_() for _ in range(self.model.total)]
+                self.ctx.run(trace.call_constraint, constraint, lambda *args: self._model_at(args, None, calls, discover=True), *cols)
+            specs = [trace.StreamSpec(sc.requested, hp=lay.hp, allact=self.model.net.allact) for sc, in calls]
+            if self.custom_forward and len(specs) > 1 and any(spec.nd for spec in specs):
+                raise NotImplementedError('a constraint that differentiates a model with its own forward() may call the model once: `D` of '
+                                          'an expression of its value finds the streams of ONE call')
+            return specs, None
+        except NotImplementedError as err:
+            return err, None
+        except Exception as err:        # noqa: BLE001 -- whatever the user's code does with stand-in values
+            return None, f'{type(err).__name__}: {err}'         # (kept per constraint in `constraint_dry_run_errors`)
+
+    def _compile_constraint(self, num, constraint):
+        """ lower constraint `num` where the fused step can serve it, and find the streams its model calls need on the generic step """
+        plan, err = self._try_compile_constraint(constraint)
+        specs, dry_run_error = self._discover_constraint(constraint)
+        for values, value in ((self.constraint_plans, plan), (self.constraint_errors, err), (self.constraint_specs, specs),
+                              (self.constraint_dry_run_errors, dry_run_error)):
+            if num < len(values):
+                values[num] = value
+            else:
+                values.append(value)
+
     def _generic_step(self, xs, loss_terms, nums_constraints, criterion, world, probe=None):
         """ probe: a dict -- the step is a DRY evaluation that is asked which parts of the graph the loss reaches (_unreached_scalars): every
         kernel stream is a leaf of its own, the backward stops at the streams, and `probe` receives 'streams' (per stream: did it get a
@@ -1712,16 +1874,7 @@ class Solver:
                     self._imap = self._input_map(xs)
                     if self._imap is not None:
                         kpts = self._imap[0]
-                if len(spec.groups) == 1:
-                    leaf = model.net.jet_forward(model.flat, kpts, spec.dir_cols, spec.n2p,
-                                                 ic_const=model.kernel_ic_const()).requires_grad_()
-                else:
-                    # more directions than one kernel call carries: one forward per group of directions (u comes with each)
-                    leaf = torch.empty((spec.n_streams, xs.shape[0]), dtype=torch.float32, device=self.device)
-                    for num, (dirs_g, n2g, idx) in enumerate(spec.groups):
-                        part = model.net.jet_forward(model.flat, kpts, dirs_g, n2g, ic_const=model.kernel_ic_const())
-                        leaf.index_copy_(0, self._group_rows(num, idx), part)
-                    leaf.requires_grad_()
+                leaf = self._streams_forward(kpts, spec).requires_grad_()
                 if probe is not None:
                     leaf = [row.detach().requires_grad_() for row in leaf.detach().unbind(0)]
                 ic_streams = None
@@ -1731,36 +1884,43 @@ class Solver:
                 term = criterion(r, torch.zeros_like(xs[:, :1]))                        # :448
                 loss = loss + (term if world == 1 else term * w_eq)
 
-            def _forward(*pts):                                                          # :451-454
-                out = model(self._points_on_device(pts))
-                if probe is not None and out.requires_grad:
-                    out.register_hook(lambda g: probe.__setitem__('value', True))
-                return out
-
+            calls = []          # model calls of the constraint terms that carry derivative streams (_model_at)
             cols = [xs[:, c:c + 1] for c in range(model.total)]
             for num in nums_constraints:                                                  # :456-457
-                term = criterion(self.ctx.run(self.constraints[num], _forward, *cols), torch.zeros(1, device=self.device))
+                specs = self.constraint_specs[num] if num < len(self.constraint_specs) else None
+                if isinstance(specs, Exception):
+                    raise specs                 # (what the dry run of this constraint met: an order or partial the kernels do not carry)
+                todo = list(specs) if specs is not None else None
+                differentiates = specs is not None and any(spec_c.nd for spec_c in specs)
+                cols_c = cols
+                if differentiates:
+                    # (leaves of the constraint's own: `D(x * f(x, t), x)` has an explicit partial derivative with respect to the batch
+                    #  column, and the ansatz of a custom forward() is torch code of the points. `D` finds them by identity all the same.)
+                    cols_c = [col.clone().requires_grad_() for col in cols]
+
+                def _forward(*pts):                                                      # :451-454
+                    if differentiates and not todo:
+                        raise NotImplementedError(f'constraint {num} calls the model more often in the step than in its dry run on stand-in '
+                                                  f'values ({len(specs)} calls): which derivative streams the further calls need is not known')
+                    spec_c = todo.pop(0) if todo else None
+                    return self._model_at(pts, spec_c, calls, probe)
+                value = self.ctx.run(trace.call_constraint, self.constraints[num], _forward, *cols_c)
+                term = criterion(value, torch.zeros(1, device=self.device))
                 loss = loss + (term if world == 1 else term * w_con)
             loss.backward()
             if probe is not None:
                 probe['streams'] = [] if leaf is None else [row.grad is not None for row in leaf]
                 probe['variables'] = {name for name in model.variables if getattr(model, name).grad is not None}
                 probe['log_scale'] = model.log_scale.grad is not None
-            elif leaf is not None and leaf.grad is not None:
-                if len(spec.groups) == 1:
-                    ws = model.workspace(xs.shape[0], spec.nd, spec.n2p)
-                    model.net.jet_backward(model.flat, kpts, leaf.grad.contiguous(), self.grads, ws, spec.dir_cols, spec.n2p,
-                                           ic_const=model.kernel_ic_const(), accumulate=True)
-                else:
-                    # the parameter gradient is linear in the upstream stream gradients: one backward per group, the
-                    # gradient of u itself rides with the first group only
-                    for num, (dirs_g, n2g, idx) in enumerate(spec.groups):
-                        gin = leaf.grad.index_select(0, self._group_rows(num, idx))
-                        if num > 0:
-                            gin[0].zero_()
-                        ws = model.workspace(xs.shape[0], len(dirs_g), n2g)
-                        model.net.jet_backward(model.flat, kpts, gin, self.grads, ws, dirs_g, n2g,
-                                               ic_const=model.kernel_ic_const(), accumulate=True)
+                for _, spec_c, rows, _ in calls:
+                    if self._streams_reach_value([row.grad is not None for row in rows], spec_c):
+                        probe['value'] = True
+            else:
+                if leaf is not None and leaf.grad is not None:
+                    self._streams_backward(kpts, spec, leaf.grad)
+                for kpts_c, spec_c, rows, slot in calls:
+                    if rows.grad is not None:
+                        self._streams_backward(kpts_c, spec_c, rows.grad, slot)
             for name, (off, n) in model.variables.items():
                 p = getattr(model, name)
                 if p.grad is not None:

@@ -31,18 +31,38 @@ def D(y, x):
     alpha = getattr(y, '_pinn_alpha', None)
     col = getattr(x, '_pinn_col', None)
     sc = trace.active_streams.get()
+    if alpha is not None and y._pinn_ctx.args is not None:
+        # the value (or a derivative stream) of a model call a CONSTRAINT made at points of its own: `x` is one of the tensors the model
+        # was called with, and the derivative is the kernel stream along that column -- picked, not differentiated
+        ctx = y._pinn_ctx
+        cols = ctx.columns_of(x)
+        if cols is None:
+            ctx.refuse_unrelated(x)
+        return ctx.derivative_along(alpha, cols)
     if alpha is not None and col is not None:
         return y._pinn_ctx.derivative(alpha, col)
-    if sc is not None and col is not None and y.requires_grad:
-        sc.used_autograd_fallback = True
+    # an expression of streams: chain rule over the streams of every context `x` is a column of -- the equation's one context, or, inside a
+    # constraint, the context of EVERY model call the constraint has made so far (`D(f(a, t) - f(b, t), t)`: both calls' streams)
+    pairs = []
+    if sc is not None and sc.args is not None:
+        pairs = [(c, c.columns_of(x)) for c in (sc.group if sc.group is not None else [sc])]
+        pairs = [(c, cols) for c, cols in pairs if cols is not None]
+    elif sc is not None and col is not None:
+        pairs = [(sc, (col, ))]
+    if pairs and y.requires_grad:
+        for c, _ in pairs:
+            c.used_autograd_fallback = True
         AUTOGRAD_FALLBACKS[0] += 1
-        items = [(a, t) for a, t in sc.stream_tensors() if t.requires_grad]
-        wrt = [x] + [t for _, t in items]
-        grads = torch.autograd.grad(y.sum(), wrt, retain_graph=True, create_graph=True, allow_unused=True)
-        total = grads[0] if grads[0] is not None else torch.zeros_like(x)
-        for (a, _), g in zip(items, grads[1:]):
+        items = [(c, cols, a, t) for c, cols in pairs for a, t in c.stream_tensors() if t.requires_grad]
+        # (x itself is always asked: the explicit partial derivative of `D(x * f(x, t), x)`. The batch columns a differentiating constraint
+        #  gets are leaves that require grad for this -- Solver._generic_step)
+        wrt = [x] + [t for _, _, _, t in items]
+        grads = list(torch.autograd.grad(y.sum(), wrt, retain_graph=True, create_graph=True, allow_unused=True))
+        explicit = grads.pop(0)
+        total = explicit if explicit is not None else torch.zeros_like(x)
+        for (c, cols, a, _), g in zip(items, grads):
             if g is not None:
-                total = total + g * sc.derivative(a, col)
+                total = total + g * c.derivative_along(a, cols)
         return total
     if sc is not None:
         sc.used_autograd_fallback = True

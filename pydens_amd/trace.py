@@ -24,6 +24,10 @@ import torch
 from .engine import OPS, MAX_OPS, MAX_CONSTS, MAX_REGS, MAX_DIRS, MAX_AUX, MAX_VARS, RES_AFFINE, RES_PROGRAM
 
 active_streams = ContextVar('pinn_active_streams', default=None)
+# during `symbolic_constraint`: the arguments of the constraint's one model call, one per column of its points (None: no call yet / no trace)
+_constraint_args = ContextVar('pinn_constraint_args', default=None)
+# while a constraint runs on the generic step (`call_constraint`): the stream contexts of the model calls it has made so far
+constraint_contexts = ContextVar('pinn_constraint_contexts', default=None)
 # during `symbolic`: maps a trainable V(...) parameter to its user slot (or None), see Solver._variable_slot
 _variable_slot = ContextVar('pinn_variable_slot', default=None)
 
@@ -250,6 +254,45 @@ class StreamContext:
         # derivatives with respect to the NETWORK's input columns, taken at ys; a derivative with respect to a column of the solver is
         # sum_k stream_{alpha + k} * d ys_k / d x_col (chain rule; the Jacobian of phi by torch autograd on the user's few pointwise ops)
         self.ymap = None           # {'cols': the solver's column tensors, 'pattern': [k][col] "ys_k depends on x_col", 'ys': None, 'jac': {}}
+        # a constraint's model call `f(*args)` (Solver._generic_step): the streams are taken at points of the constraint's own choosing, and
+        # `D(value, x)` finds the columns to differentiate along from the IDENTITY of `x` among the call's arguments (None: the equation's
+        # context, whose columns carry `_pinn_col`)
+        self.args = None           # [argument object per column of the points]
+        self.group = None
+
+    def bind_args(self, args):
+        self.args = list(args)
+        # the contexts of ALL model calls of the running constraint, this one included (`D` of an expression of several calls' values)
+        self.group = constraint_contexts.get()
+        if self.group is not None:
+            self.group.append(self)
+        return self
+
+    def columns_of(self, x):
+        """ the columns of this call's points that ARE the tensor `x` (by identity; `f(p, p)`: both). None: `x` is none of the arguments. """
+        cols = tuple(c for c, arg in enumerate(self.args or ()) if arg is x)
+        return cols or None
+
+    def refuse_unrelated(self, x):
+        """ `D(value, x)` with an `x` that is no argument of the model call: a function of one (the reference differentiates through it;
+        not built here) or something the points do not depend on (an error in the reference too) """
+        if torch.is_tensor(x):
+            for arg in self.args or ():
+                if torch.is_tensor(arg) and arg.requires_grad and arg.grad_fn is not None and x.requires_grad:
+                    if torch.autograd.grad(arg.sum(), x, retain_graph=True, allow_unused=True)[0] is not None:
+                        raise NotImplementedError('D(f(...), x) with an argument of f that is a FUNCTION of x (f(2 * x), f(x + h)): pass x itself '
+                                                  'to the model and differentiate with respect to it; the chain rule through a map of the '
+                                                  "constraint's own points is not built")
+        raise RuntimeError('D(f(...), x): x is none of the tensors the model was called with -- the points do not depend on it '
+                           '(torch: "One of the differentiated Tensors appears to not have been used in the graph")')
+
+    def derivative_along(self, alpha, cols):
+        """ d stream_alpha / d x for an `x` that feeds the columns `cols` of the points: the sum of the partial derivatives """
+        total = None
+        for col in cols:
+            term = self.derivative(alpha, col)
+            total = term if total is None else total + term
+        return total
 
     def tag(self, tensor, alpha):
         tensor._pinn_alpha = alpha
@@ -298,6 +341,17 @@ def call_with_streams(sc, equation, *args):
         return equation(*args)
     finally:
         active_streams.reset(token)
+
+
+def call_constraint(constraint, forward, *cols):
+    """ run a constraint callable `constraint(f, *xs)` (must itself be what `ctx.run` invokes, cf. call_with_streams): every model call it
+    makes sets the active stream context to its own (Solver._model_at), and nothing of that outlives the constraint """
+    token, calls = active_streams.set(None), constraint_contexts.set([])
+    try:
+        return constraint(forward, *cols)
+    finally:
+        active_streams.reset(token)
+        constraint_contexts.reset(calls)
 
 
 def discover(equation, ctx_run, n_inputs, device='cpu', hp=None, allact=False):
@@ -354,12 +408,19 @@ class Sym:
 
     def __init__(self, kind, op=None, args=(), value=None, alpha=None, col=None):
         self.kind, self.op, self.args, self.value, self.alpha, self.col = kind, op, tuple(args), value, alpha, col
+        self.batch = False          # an 'input' that is a column of the BATCH while a constraint is traced (its own points' columns are not)
 
     # -- construction helpers ------------------------------------------------------------------------------------
     @staticmethod
     def wrap(value):
         if isinstance(value, Sym):
             return value
+        args = _constraint_args.get()
+        if args is not None and torch.is_tensor(value) and not isinstance(value, torch.nn.Parameter):
+            # a tensor the constraint also CALLED the model with (`f(xg, t0)` ... `V('v0') * xg`): that column of the constraint's points
+            cols = [c for c, arg in enumerate(args) if arg is value]
+            if len(cols) == 1:
+                return Sym('input', col=cols[0])
         const = _as_const(value)
         if const is None:                       # a scalar trainable V(...): lives in a program register of its own
             return Sym('var', col=_variable_slot.get()(value))
@@ -431,6 +492,10 @@ class Sym:
             return lambda e: self ** e
         if name == 'square':
             return lambda: Sym.make('MUL', self, self)
+        if name == 'requires_grad_':
+            # (`t0 = torch.zeros_like(t).requires_grad_()`: a leaf made from a batch column -- still a thing of the batch, and a model call
+            #  on it is refused as such)
+            return lambda *args, **kwargs: self
         raise TraceUnsupported(f'tensor attribute .{name} is not expressible in a residual program')
 
 
@@ -526,7 +591,17 @@ def _differentiate(node, col, memo):
 def sym_D(y, x):
     """ `D` on symbolic operands: d(stream)/d(input column) is the next stream; composite expressions -- D(f * f, x),
     D(a(x) * D(f, x), x) -- are differentiated symbolically (chain rule down to the streams). """
-    if not (isinstance(x, Sym) and x.kind == 'input'):
+    if not isinstance(x, Sym):
+        # a constraint differentiates the model with respect to a tensor it was called with: that column (those columns) of its points
+        args = _constraint_args.get()
+        cols = [c for c, arg in enumerate(args or ()) if arg is x]
+        if not cols:
+            raise TraceUnsupported('D with respect to something that is neither an input column nor an argument of the model call')
+        total = Sym('const', value=0.0)
+        for col in cols:
+            total = _s_add(total, _differentiate(Sym.wrap(y), col, {}))
+        return total
+    if x.kind != 'input':
         raise TraceUnsupported('D with respect to something that is not an input column')
     return _differentiate(Sym.wrap(y), x.col, {})
 
@@ -558,7 +633,7 @@ def symbolic(equation, ctx_run, n_inputs, variable_slot=None):
 def _depends_on_inputs(node, memo):
     key = id(node)
     if key not in memo:
-        memo[key] = node.kind == 'input' or any(_depends_on_inputs(a, memo) for a in node.args)
+        memo[key] = (node.kind == 'input' and node.batch) or any(_depends_on_inputs(a, memo) for a in node.args)
         _keep(memo, node)
     return memo[key]
 
@@ -568,7 +643,9 @@ def symbolic_constraint(constraint, ctx_run, n_inputs, to_points, variable_slot=
     whatever points it is given, e.g. `lambda f, x: f(torch.tensor([0.5]))`). Supported form: ONE call of `f` on
     constants -- numbers, arrays, tensors, cast by `to_points` exactly like the reference's `reshape_and_concat` -- and
     a pointwise expression of its value and trainable variables that does not touch the batch columns.
-    Returns (root Sym over the value stream, points [n_c, n_inputs] float32). Raises TraceUnsupported otherwise. """
+    The tensors the model was called with are remembered, one per column of the points: `D(value, arg)` differentiates symbolically along
+    that column (`sym_D`), and the same tensor met as an operand (`V('v0') * xg`) is that column of the constraint's points.
+    Returns (root Sym over the streams, points [n_c, n_inputs] float32). Raises TraceUnsupported otherwise. """
     calls = []
 
     def model_at(*args):
@@ -576,15 +653,25 @@ def symbolic_constraint(constraint, ctx_run, n_inputs, to_points, variable_slot=
             raise TraceUnsupported('constraint evaluates the model on the batch points')
         if calls:
             raise TraceUnsupported('constraint evaluates the model more than once')
-        pts = np.asarray(to_points(args), dtype=np.float32)
+        pts = np.asarray(to_points([a.detach().cpu() if torch.is_tensor(a) else a for a in args]), dtype=np.float32)
         if pts.ndim != 2 or pts.shape[1] != n_inputs:
             raise TraceUnsupported(f'constraint calls the model with {pts.shape[-1]} columns, the problem has {n_inputs}')
         calls.append(pts)
+        _constraint_args.set(list(args))
         return Sym('stream', alpha=())
 
+    def run(*args):
+        token = _constraint_args.set(None)
+        try:
+            return _call_with_variables(*args)
+        finally:
+            _constraint_args.reset(token)
+
     xs = [Sym('input', col=c) for c in range(n_inputs)]
+    for x in xs:
+        x.batch = True
     try:
-        root = ctx_run(_call_with_variables, variable_slot, constraint, model_at, *xs)
+        root = ctx_run(run, variable_slot, constraint, model_at, *xs)
     except TraceUnsupported:
         raise
     except (TypeError, ValueError, AttributeError, RuntimeError, LookupError) as err:
@@ -594,6 +681,22 @@ def symbolic_constraint(constraint, ctx_run, n_inputs, to_points, variable_slot=
     if _depends_on_inputs(root, {}):
         raise TraceUnsupported('constraint depends on the batch points')
     return root, calls[0]
+
+
+def requested_streams(root):
+    """ the multi-indices a traced expression reads: what `StreamSpec` is built from (('d', a, b) is the diagonal of the mixed u_ab) """
+    found, seen = set(), set()
+
+    def walk(node):
+        if id(node) in seen:
+            return
+        seen.add(id(node))
+        if node.kind == 'stream' and node.alpha:
+            found.add(tuple(node.alpha[1:]) if node.alpha[0] == 'd' else tuple(node.alpha))
+        for a in node.args:
+            walk(a)
+    walk(root)
+    return found
 
 
 def kernel_stream_shift(nd, n2p):
