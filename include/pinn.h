@@ -545,6 +545,42 @@ int pinn_lbfgs_direction(float* params, const float* grads, float* prev_grad, fl
                          double tolerance_grad, double tolerance_change, void* ctrl, size_t ctrl_bytes, void* workspace,
                          size_t workspace_bytes, void* stream);
 
+/* Loss-term weights: the terms of a loss kept apart for one more step and combined on the device -- three launches whatever the
+ * number of terms (pydens_amd/csrc/pinn_balance_kernels.h: statistics of every term in one pass, the weight rule on at most eight
+ * scalars in fp64, one combination pass). The caller evaluates every term into a row of its own and owns every buffer.
+ *   term_grads   [n_terms][ld] row j: the gradient buffer term j wrote on its own, its loss in entry off_loss; ld % 4 == 0, ld >= n
+ *   mask         [n] or null. LIVE entries: i < n, i != off_loss, mask[i] != 0 (no mask: all of those). Every other entry -- padding, a
+ *                frozen entry, an unreached scalar, the loss slot -- enters no statistic and is never written in grads_out
+ *   kind         PINN_BALANCE_FIXED: the weights stay as the state holds them.
+ *                PINN_BALANCE_MAX_MEAN (Wang, Teng, Perdikaris 2021): hat_ref = 1, hat_i = max|g_ref| / (sum|g_i| / live count), i != ref.
+ *                PINN_BALANCE_NORM: hat_i = (sum_j |g_j|_2) / |g_i|_2 for every term, j over the terms with finite statistics.
+ *                Then w_i <- momentum * w_i + (1 - momentum) * hat_i, clipped to [lo, hi] (0 <= lo <= hi, finite; momentum in [0, 1]).
+ *                A term KEEPS its weight in this call if its denominator is 0, one of its live entries is NaN or infinite, or its hat
+ *                is not finite; under MAX_MEAN all terms keep theirs if max|g_ref| is 0 or the reference term is non-finite.
+ *   update       0: no weight changes in this call (a rule applied every k-th iteration); the statistics are still taken
+ *   state        pinn_balance_state_bytes, doubles: [0..8) the weights  [8] calls so far that ran the rule  [9] live count of the last
+ *                call, and the last call's statistics by term: [16..24) max|g|  [24..32) sum|g|  [32..40) sum g^2  [40..48) 1: non-finite.
+ *                pinn_balance_init fills it: the given weights (host memory, finite, >= 0), everything else zero
+ *   grads_out    [n] live entries: fl32(sum_j w_j g_j[i]), the sum in fp64 in ascending j, one rounding; grads_out[off_loss] takes
+ *                fl32(sum_j w_j L_j), the weighted loss. It MAY be row 0 of term_grads itself (every entry is read and written by one
+ *                thread, reads first); any other overlap with the term rows is refused
+ *   term_loss_out, weight_out  [n_terms] floats or null, written by the last launch (as loss_out of the optimizer entry points is):
+ *                the unweighted L_j and fl32(w_j) as they stand behind this call's update; they must not overlap the other buffers
+ *   workspace    rows of partial statistics, the size the workspace_bytes query returns
+ * term_grads, grads_out, state and workspace 16-byte aligned. Bit-repeatable: no atomics, no waits between workgroups, fixed summation
+ * orders: max|g| and the live count are exact, the sums carry fp64 rounding only (a product of two fp32 values is exact in fp64).
+ * Nothing synchronises and nothing is read back. A refused call (non-zero, pinn_last_error) has launched nothing. */
+#define PINN_BALANCE_MAX_TERMS 8
+#define PINN_BALANCE_FIXED 0
+#define PINN_BALANCE_MAX_MEAN 1
+#define PINN_BALANCE_NORM 2
+size_t pinn_balance_state_bytes(int32_t n_terms);
+size_t pinn_balance_workspace_bytes(int64_t n, int32_t n_terms);
+int pinn_balance_init(void* state, size_t state_bytes, int32_t n_terms, const double* weights, void* stream);
+int pinn_balance_terms(const float* term_grads, int64_t ld, int32_t n_terms, int64_t n, const uint8_t* mask, int32_t off_loss, int32_t kind,
+                       int32_t ref_term, int32_t update, double momentum, double lo, double hi, void* state, size_t state_bytes,
+                       float* grads_out, float* term_loss_out, float* weight_out, void* workspace, size_t workspace_bytes, void* stream);
+
 /* Residual-adaptive collocation sampling (RAD: Wu et al., CMAME 2023): n_out rows of `pool` [m][d] (fp32, row-major, d <= 8,
  * m <= 2^22) drawn with replacement with probability proportional to q_i = w_i + floor_c * mean(w), w_i = |r_i|^power in double
  * (power 1 or 2; a non-finite r_i has weight 0), mean(w) = sum(w) / m.  Inverse CDF over the inclusive fp64 prefix sums P of q:

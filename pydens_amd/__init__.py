@@ -8,6 +8,7 @@ CPU or eager-PyTorch fallback: constructing a Solver without the built library o
 from .tokens import D, V, current_model
 from .model import TorchModel, ConvBlockModel
 from .solver import Solver
+from .balance import LossBalancer
 from .sampler import *            # noqa: F401,F403  (reference re-exports batchflow.sampler.*)
 from .sampler import NumpySampler, NS, Sampler, ConstantSampler, ResidualSampler
 

@@ -5,6 +5,7 @@
 #include "pinn_aux_kernels.h"
 #include "pinn_port_probe.h"
 #include "pinn_lbfgs_kernels.h"
+#include "pinn_balance_kernels.h"
 
 #include <atomic>
 #include <cfloat>
@@ -1573,6 +1574,81 @@ int pinn_lbfgs_direction(float* params, const float* grads, float* prev_grad, fl
         launch("L-BFGS kernel", pinn_lbfgs_finalize_kernel, 1, PINN_LBFGS_THREADS, smem_fin, stream, A))
         return 1;
     return launch("L-BFGS kernel", pinn_lbfgs_combine_kernel, blocks, PINN_LBFGS_THREADS, 0, stream, A);
+}
+
+// ---- loss-term weights (pinn_balance_kernels.h): three launches per call, whatever the number of terms ---------------------------------
+static_assert(PINN_BALANCE_STATE_DOUBLES % 2 == 0, "the state block is a whole number of 16-byte pieces");
+
+size_t pinn_balance_state_bytes(int32_t n_terms) {
+    if (n_terms < 1 || n_terms > PINN_BALANCE_MAX_TERMS) return 0;
+    return (size_t)PINN_BALANCE_STATE_DOUBLES * sizeof(double);
+}
+
+size_t pinn_balance_workspace_bytes(int64_t n, int32_t n_terms) {
+    if (n < 1 || n > (int64_t)1 << 40 || n_terms < 1 || n_terms > PINN_BALANCE_MAX_TERMS) return 0;
+    const size_t rows = (size_t)((n + PINN_BALANCE_STATS_SLICE - 1) / PINN_BALANCE_STATS_SLICE);
+    return (rows * (size_t)PINN_BALANCE_ROWLEN(n_terms) * sizeof(double) + 15) / 16 * 16;
+}
+
+int pinn_balance_init(void* state, size_t state_bytes, int32_t n_terms, const double* weights, void* stream) {
+    if (n_terms < 1 || n_terms > PINN_BALANCE_MAX_TERMS)
+        return fail("loss weights: n_terms=%d outside [1, %d]", n_terms, PINN_BALANCE_MAX_TERMS);
+    if (!state || !weights) return fail("loss weights: null argument");
+    if (reinterpret_cast<uintptr_t>(state) & 15) return fail("loss weights: the state block must be 16-byte aligned");
+    if (state_bytes < pinn_balance_state_bytes(n_terms))
+        return fail("loss weights: state block too small (%zu < %zu bytes)", state_bytes, pinn_balance_state_bytes(n_terms));
+    PinnBalanceArgs A = {};
+    A.T = n_terms;
+    A.state = static_cast<double*>(state);
+    for (int j = 0; j < n_terms; ++j) {
+        if (!(weights[j] >= 0.0 && weights[j] <= DBL_MAX)) return fail("loss weights: weight %d is %g; a weight is finite and not negative", j, weights[j]);
+        A.init[j] = weights[j];
+    }
+    return launch("loss-weight kernel", pinn_balance_init_kernel, 1, PINN_BALANCE_THREADS, 0, stream, A);
+}
+
+int pinn_balance_terms(const float* term_grads, int64_t ld, int32_t n_terms, int64_t n, const uint8_t* mask, int32_t off_loss, int32_t kind,
+                       int32_t ref_term, int32_t update, double momentum, double lo, double hi, void* state, size_t state_bytes,
+                       float* grads_out, float* term_loss_out, float* weight_out, void* workspace, size_t workspace_bytes, void* stream) {
+    if (n_terms < 1 || n_terms > PINN_BALANCE_MAX_TERMS)
+        return fail("loss weights: n_terms=%d outside [1, %d]", n_terms, PINN_BALANCE_MAX_TERMS);
+    if (!term_grads || !state || !grads_out || !workspace) return fail("loss weights: null argument");
+    if (n < 1 || n > (int64_t)1 << 40) return fail("loss weights: n=%lld entries", (long long)n);
+    if (ld < n || ld % 4 != 0)
+        return fail("loss weights: row stride %lld of the term rows must be a multiple of 4 and at least n=%lld", (long long)ld, (long long)n);
+    if (off_loss < 0 || off_loss >= n) return fail("off_loss=%d outside the gradient buffer", off_loss);
+    if (kind != PINN_BALANCE_FIXED && kind != PINN_BALANCE_MAX_MEAN && kind != PINN_BALANCE_NORM)
+        return fail("loss weights: unknown kind %d (0 fixed, 1 max / mean, 2 norm)", kind);
+    if (ref_term < 0 || ref_term >= n_terms) return fail("loss weights: ref_term=%d outside [0, %d)", ref_term, n_terms);
+    if (!(momentum >= 0.0 && momentum <= 1.0)) return fail("loss weights: momentum=%g outside [0, 1]", momentum);
+    if (!(lo >= 0.0 && lo <= hi && hi <= DBL_MAX)) return fail("loss weights: clip [%g, %g] must be finite with 0 <= lo <= hi", lo, hi);
+    const void* aligned[] = {term_grads, state, grads_out, workspace};
+    for (const void* p : aligned)
+        if (reinterpret_cast<uintptr_t>(p) & 15) return fail("loss weights: buffers must be 16-byte aligned");
+    if ((reinterpret_cast<uintptr_t>(term_loss_out) | reinterpret_cast<uintptr_t>(weight_out)) & 3)
+        return fail("loss weights: term_loss_out and weight_out must be 4-byte aligned");
+    // the combine pass reads entry i of every row and writes entry i of the output in ONE thread, reads first: the output may be row 0
+    // itself. Any other overlap with the term rows would have one workgroup write what another still reads: refused.
+    const float* rows_end = term_grads + (size_t)(n_terms - 1) * (size_t)ld + (size_t)n;
+    if (grads_out != term_grads && grads_out < rows_end && grads_out + n > term_grads)
+        return fail("loss weights: grads_out overlaps the term rows (it may be row 0 itself, nothing else of them)");
+    if (state_bytes < pinn_balance_state_bytes(n_terms))
+        return fail("loss weights: state block too small (%zu < %zu bytes)", state_bytes, pinn_balance_state_bytes(n_terms));
+    if (workspace_bytes < pinn_balance_workspace_bytes(n, n_terms))
+        return fail("workspace too small (%zu < %zu bytes)", workspace_bytes, pinn_balance_workspace_bytes(n, n_terms));
+    const int blocks = (int)((n + PINN_BALANCE_SLICE - 1) / PINN_BALANCE_SLICE);                       // the combine pass
+    const int rows = (int)((n + PINN_BALANCE_STATS_SLICE - 1) / PINN_BALANCE_STATS_SLICE);             // the stats pass: one row of partials each
+    PinnBalanceArgs A = {};
+    A.g = term_grads; A.out = grads_out; A.mask = mask; A.n = (long long)n; A.ld = (long long)ld;
+    A.T = n_terms; A.off_loss = off_loss; A.kind = kind; A.ref = ref_term; A.update = update ? 1 : 0;
+    A.momentum = momentum; A.lo = lo; A.hi = hi;
+    A.state = static_cast<double*>(state); A.rows = static_cast<double*>(workspace); A.n_rows = rows;
+    A.term_loss_out = term_loss_out; A.weight_out = weight_out;
+    const size_t rowlen = (size_t)PINN_BALANCE_ROWLEN(n_terms);
+    if (launch("loss-weight kernel", pinn_balance_stats_kernel, rows, PINN_BALANCE_THREADS, 4 * rowlen * sizeof(double), stream, A) ||
+        launch("loss-weight kernel", pinn_balance_finalize_kernel, 1, PINN_BALANCE_THREADS, rowlen * sizeof(double), stream, A))
+        return 1;
+    return launch("loss-weight kernel", pinn_balance_combine_kernel, blocks, PINN_BALANCE_THREADS, 0, stream, A);
 }
 
 // ---- residual-adaptive resampler (pinn_aux_kernels.h: three launches; the redraw is the third alone) -----------------------------------

@@ -24,6 +24,10 @@ LBFGS_MAX_HISTORY = 128                                            # include/pin
 # the first doubles of pinn_lbfgs_direction's control block
 LBFGS_CTRL = ('count', 'head', 'n_iter', 'H_diag', 't', 'gtd', 'gmax', 'smax', 'loss', 'prev_loss', 'ys', 'yy', 'stop', 'pushed', 'slot', 'c_g')
 LBFGS_START, LBFGS_LOOP = 0, 1                                     # `mode` of pinn_lbfgs_direction
+BALANCE_MAX_TERMS = 8                                              # include/pinn.h PINN_BALANCE_MAX_TERMS
+BALANCE_FIXED, BALANCE_MAX_MEAN, BALANCE_NORM = 0, 1, 2            # include/pinn.h PINN_BALANCE_*: `kind` of pinn_balance_terms
+# pinn_balance_terms' state block, in doubles: (first, count) of every field
+BALANCE_STATE = dict(weights=(0, 8), updates=(8, 1), count=(9, 1), gmax=(16, 8), sum_abs=(24, 8), sum_sq=(32, 8), non_finite=(40, 8))
 SKIP_PRE = 0x100         # include/pinn.h PINN_SKIP_PRE
 ACT_CODES = {'tanh': 0, 'sigmoid': 1, 'sin': 2, 'identity': 3, 'softplus': 4, 'silu': 5, 'swish': 5, 'gelu': 6,
              # round 5 (include/pinn.h PINN_ACT_RELU ..): torch-default forms
@@ -199,6 +203,15 @@ def bind(lib):
     lib.pinn_lbfgs_direction.argtypes = [vp, vp, vp, vp, vp, vp, vp, i64, i64, i32, i32, i32, i32, f32, f64, f64, f64, vp, ctypes.c_size_t,
                                          vp, ctypes.c_size_t, vp]
     lib.pinn_lbfgs_direction.restype = i32
+    lib.pinn_balance_state_bytes.argtypes = [i32]
+    lib.pinn_balance_state_bytes.restype = ctypes.c_size_t
+    lib.pinn_balance_workspace_bytes.argtypes = [i64, i32]
+    lib.pinn_balance_workspace_bytes.restype = ctypes.c_size_t
+    lib.pinn_balance_init.argtypes = [vp, ctypes.c_size_t, i32, ctypes.POINTER(f64), vp]
+    lib.pinn_balance_init.restype = i32
+    lib.pinn_balance_terms.argtypes = [vp, i64, i32, i64, vp, i32, i32, i32, i32, f64, f64, f64, vp, ctypes.c_size_t, vp, vp, vp, vp,
+                                       ctypes.c_size_t, vp]
+    lib.pinn_balance_terms.restype = i32
     u64 = ctypes.c_uint64
     lib.pinn_resample_workspace_bytes.argtypes = [i64]
     lib.pinn_resample_workspace_bytes.restype = ctypes.c_size_t
@@ -219,6 +232,7 @@ ABI_SYMBOLS = ('pinn_create', 'pinn_create_ex', 'pinn_destroy', 'pinn_layout', '
                'pinn_optim_step', 'pinn_optim_step_at', 'pinn_residual_optim_step', 'pinn_fit_steps_optim', 'pinn_fit_steps_optim_graph',
                'pinn_fit_steps_optim_sched', 'pinn_reduce_rows', 'pinn_last_reduce_kernel_name', 'pinn_port_probe',
                'pinn_lbfgs_ctrl_bytes', 'pinn_lbfgs_workspace_bytes', 'pinn_lbfgs_direction',
+               'pinn_balance_state_bytes', 'pinn_balance_workspace_bytes', 'pinn_balance_init', 'pinn_balance_terms',
                'pinn_resample_workspace_bytes', 'pinn_resample_points', 'pinn_resample_redraw',
                'pinn_last_error', 'pinn_backend')
 
@@ -585,6 +599,43 @@ class Net:
                 int(mode), int(bool(apply_step)), int(self.layout.off_loss if off_loss is None else off_loss), float(t), float(lr),
                 float(tolerance_grad), float(tolerance_change), _ptr(ctrl), ctrl.numel() * 8, _ptr(workspace),
                 workspace.numel() * workspace.element_size(), _stream(params) if stream is None else stream))
+
+    # ---- loss-term weights (include/pinn.h pinn_balance_terms) ------------------------------------------------------------------------
+    def balance_state(self, n_terms, weights, device, state=None, stream=None):
+        """ the state block of pinn_balance_terms (float64 tensor) holding `weights`, one per term, everything else zero """
+        need = int(self.lib.pinn_balance_state_bytes(int(n_terms)))
+        if need == 0:
+            raise ValueError(f'loss weights: {n_terms} terms; the kernels carry 1 to {BALANCE_MAX_TERMS}')
+        if state is None:
+            state = torch.zeros(need // 8, dtype=torch.float64, device=device)
+        _check(state, 'state', torch.float64)
+        host = (ctypes.c_double * int(n_terms))(*[float(w) for w in weights])
+        with _on_device(state):
+            self._raise(self.lib.pinn_balance_init(_ptr(state), state.numel() * 8, int(n_terms), host, _stream(state) if stream is None else stream))
+        return state
+
+    def balance_workspace(self, n, n_terms, device):
+        need = int(self.lib.pinn_balance_workspace_bytes(int(n), int(n_terms)))
+        if need == 0:
+            raise ValueError(f'loss weights: n={n}, {n_terms} terms is outside the range of the kernels')
+        return torch.empty(need // 8, dtype=torch.float64, device=device)
+
+    def balance_terms(self, term_grads, n, mask, kind, ref_term, update, momentum, lo, hi, state, out, workspace, term_loss_out=None,
+                      weight_out=None, off_loss=None, stream=None):
+        """ out[:n] <- sum_j w_j term_grads[j, :n] over the live entries, the weights updated first by the rule `kind` (three launches;
+        include/pinn.h pinn_balance_terms). term_loss_out / weight_out: device ADDRESSES (int) or None -- rows of the caller's histories """
+        _check(term_grads, 'term_grads'); _check(out, 'out'); _check(mask, 'mask', torch.uint8)
+        _check(state, 'state', torch.float64); _check(workspace, 'workspace', torch.float64)
+        if term_grads.dim() != 2:
+            raise ValueError('term_grads must be [n_terms, ld]')
+        with _on_device(out):
+            self._raise(self.lib.pinn_balance_terms(
+                _ptr(term_grads), term_grads.shape[1], term_grads.shape[0], int(n), _ptr(mask),
+                int(self.layout.off_loss if off_loss is None else off_loss), int(kind), int(ref_term), int(bool(update)), float(momentum),
+                float(lo), float(hi), _ptr(state), state.numel() * 8, _ptr(out),
+                None if term_loss_out is None else ctypes.c_void_p(int(term_loss_out)),
+                None if weight_out is None else ctypes.c_void_p(int(weight_out)), _ptr(workspace), workspace.numel() * 8,
+                _stream(out) if stream is None else stream))
 
     # ---- residual-adaptive resampler (include/pinn.h pinn_resample_points) -----------------------------------------------------------
     def resample_workspace(self, m, device):

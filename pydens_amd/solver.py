@@ -23,6 +23,7 @@ from torch import nn
 from tqdm import tqdm
 
 from . import engine, trace
+from .balance import LossBalancer
 from .model import ConvBlockModel, InputProbe, PROBE
 from . import tokens
 from .tokens import current_model
@@ -448,6 +449,9 @@ class Solver:
         self._lr_queue = []                 # rates drawn ahead of the device, one chunk at a time; the head is the next step's
         self.optimizer_path = 'torch'       # set_optimizer_path: optimizers other than plain Adam as torch.optim code or on the fused kernels
         self.last_fit_optimizer = None
+        self.last_fit_balance = None        # fit(loss_weights=...): e.g. 'max_mean/fused', 'fixed/generic'; None: the plain sum of the terms
+        self._balance = None                # the LossBalancer of the running / last weighted fit
+        self._term_history, self._term_pending = [], []     # per weighted fit: (terms, losses [it, T], weights [it, T]) / the device histories
         self.optimizer_refusal = None       # why the last `fit(optimizer='LBFGS')` under the 'fused' path kept torch.optim (None: it did not)
         if os.environ.get('PYDENS_AMD_OPTIMIZER'):
             self.set_optimizer_path(os.environ['PYDENS_AMD_OPTIMIZER'])
@@ -1094,6 +1098,36 @@ class Solver:
     def losses(self, value):
         self._pending, self._losses = [], list(value)
 
+    def _weight_histories(self):
+        """ the device histories of the weighted fits so far, fetched lazily like `losses` """
+        for terms, term_hist, weight_hist, done in self._term_pending:
+            self._term_history.append((terms, term_hist[:done[0]].detach().cpu().numpy().copy(), weight_hist[:done[0]].detach().cpu().numpy().copy()))
+        self._term_pending = []
+        return self._term_history
+
+    def _stacked_history(self, which):
+        runs = self._weight_histories()
+        if not runs:
+            return np.zeros((0, 0), dtype=np.float32)
+        terms = runs[-1][0]         # (fits over other terms have rows of another width: the rows of the latest set of terms are returned)
+        return np.concatenate([run[which] for run in runs if run[0] == terms], axis=0)
+
+    @property
+    def term_losses(self):
+        """ [iterations, T] float32: the UNWEIGHTED loss of every term of `loss_terms`, one row per iteration of the fits with
+        `loss_weights` (those over the latest set of terms); `losses` holds the weighted sum, which is what is optimised """
+        return self._stacked_history(1)
+
+    @property
+    def loss_weight_history(self):
+        """ [iterations, T] float32: the weights each of those iterations was stepped with """
+        return self._stacked_history(2)
+
+    @property
+    def loss_weights(self):
+        """ {term: weight} of the last fit with `loss_weights`, read back from the device (None: there was none) """
+        return None if self._balance is None else self._balance.weights
+
     @classmethod
     def reshape_and_concat(cls, tensors, device=None):
         """ Input casting of reference model_torch.py:327-362 -> float32 [N, D] (on `device` if given). """
@@ -1228,11 +1262,11 @@ class Solver:
             self._comm.close()
             self._comm = None
 
-    def _all_reduce(self, stream=None):
+    def _all_reduce(self, stream=None, tensor=None):
         if self._comm is None:
             self.begin_data_parallel()
         if self._comm is not None:              # (no process group: single process, nothing to exchange)
-            self._comm.all_reduce_(self.grads, stream)
+            self._comm.all_reduce_(self.grads if tensor is None else tensor, stream)
 
     def _dp_step(self, xs, world, stream=None, loss_out=None):
         """ one data-parallel iteration on this rank's shard `xs`: tile kernel + reduction, all-reduce of the flat gradient
@@ -1315,8 +1349,84 @@ class Solver:
         `factory(optimizer) -> scheduler`; the torch loop `opt.step(); sched.step()` once per iteration, on every step path
         (`_set_scheduler`). `fit(optimizer=None)` carries the running schedule on; a new optimizer without one has a constant rate. """
         lr_scheduler, lr_scheduler_kwargs = kwargs.pop('lr_scheduler', None), kwargs.pop('lr_scheduler_kwargs', None)
+        loss_weights = kwargs.pop('loss_weights', None)
         with self._device_guard():
-            return self._fit(niters, batch_size, sampler, loss_terms, optimizer, criterion, lr, lr_scheduler, lr_scheduler_kwargs, **kwargs)
+            return self._fit(niters, batch_size, sampler, loss_terms, optimizer, criterion, lr, lr_scheduler, lr_scheduler_kwargs,
+                             loss_weights=loss_weights, **kwargs)
+
+    # ---- loss-term weights ---------------------------------------------------------------------------------------------------------
+    def _steps_by_closure(self, optimizer, lr, kwargs):
+        """ will the optimizer of the coming fit call re-evaluate the batch inside one step (`step(closure)`: L-BFGS)? """
+        if optimizer is None:
+            return bool(self.optimizer is not None and self.optimizer.needs_closure)
+        import inspect
+        cls = getattr(torch.optim, optimizer, None) if isinstance(optimizer, str) else None
+        closure = inspect.signature(cls.step).parameters.get('closure') if cls is not None else None
+        return closure is not None and closure.default is inspect.Parameter.empty
+
+    def _resolve_loss_weights(self, loss_weights, loss_terms, by_closure):
+        """ `fit(loss_weights=...)` -> the LossBalancer that serves the call (None: the plain sum, today's code), or the refusal, raised
+        before the call has changed anything: a dict by term name or a sequence aligned with `loss_terms` (constant weights), or a
+        LossBalancer (adaptive; the object owns its device state and carries it from fit to fit) """
+        if loss_weights is None:
+            return None
+        terms = tuple(loss_terms)
+        for term in terms:
+            num = term.replace('constraint', '').replace('_', '') if isinstance(term, str) and 'constraint' in term else None
+            if term != 'equation' and not (num is not None and num.isdigit() and int(num) < len(self.constraints)):
+                raise ValueError(f"loss_weights: the loss term {term!r} is neither 'equation' nor one of the {len(self.constraints)} constraints of "
+                                 'this solver; only those are evaluated term by term')
+        if len(terms) > engine.BALANCE_MAX_TERMS:
+            raise NotImplementedError(f'loss_weights: {len(terms)} loss terms; the kernels combine at most {engine.BALANCE_MAX_TERMS}')
+        if isinstance(loss_weights, LossBalancer):
+            balance = loss_weights
+        elif isinstance(loss_weights, dict):
+            balance = LossBalancer.fixed(loss_weights)
+        elif isinstance(loss_weights, (tuple, list, np.ndarray)):
+            if len(loss_weights) != len(terms):
+                raise ValueError(f'loss_weights: {len(loss_weights)} weights for the {len(terms)} terms of loss_terms={list(terms)}')
+            if len(set(terms)) != len(terms):
+                raise ValueError(f'loss_weights: loss_terms={list(terms)} names a term twice')
+            balance = LossBalancer.fixed(dict(zip(terms, [w.item() if isinstance(w, np.generic) else w for w in loss_weights])))
+        else:
+            raise ValueError(f'loss_weights={loss_weights!r}: a dict by term name, a sequence aligned with loss_terms, or a LossBalancer')
+        refusal = balance.refusal(terms, by_closure)
+        if refusal is not None:
+            raise refusal
+        return balance
+
+    def _term_rows(self, n_terms):
+        """ [T, ld] gradient rows of the weighted step, one per term (ld: p_total rounded up to a 16-byte piece), kept from fit to fit """
+        ld = (self.grads.numel() + 3) // 4 * 4
+        rows = getattr(self, '_balance_rows', None)
+        if rows is None or rows.shape != (n_terms, ld) or rows.device != self.grads.device:
+            rows = self._balance_rows = torch.zeros((n_terms, ld), dtype=torch.float32, device=self.device)
+        return rows
+
+    def _weighted_step(self, xs, loss_terms, criterion, world, fused, wb, it=None, stream=None):
+        """ the gradient part of one iteration under loss weights: every term of `loss_terms` is evaluated by the code that evaluates it in
+        the plain sum -- its gradient buffer pointed at row j of one [T, ld] tensor, accumulation off --, under torch.distributed the
+        stacked rows are all-reduced in ONE call (every rank computes the same weights), and pinn_balance_terms writes `self.grads`:
+        weighted gradient, weighted loss in the loss slot. `it`: the row of the term / weight histories this evaluation is recorded in
+        (None: not recorded -- the later evaluations of a closure step). The generic step runs eagerly, once per term. """
+        rows, n, grads = wb['rows'], self.grads.numel(), self.grads
+        try:
+            for j, term in enumerate(loss_terms):
+                self.grads = rows[j, :n]
+                if fused and term == 'equation':
+                    self._fused_step(xs, world, stream=stream)
+                elif fused:
+                    self._constraint_step(wb['nums'][j], world, accumulate=False)
+                else:
+                    self._generic_step(xs, (term, ), [] if term == 'equation' else [wb['nums'][j]], criterion, world)
+        finally:
+            self.grads = grads
+        if world > 1:
+            self._all_reduce(stream, rows)
+        record = it is not None
+        wb['balance'].combine(self.model.net, rows, n, wb['mask'], self.grads,
+                              term_loss_out=wb['term_ptr'] + 4 * len(loss_terms) * it if record else None,
+                              weight_out=wb['weight_ptr'] + 4 * len(loss_terms) * it if record else None, count=record, stream=stream)
 
     # ---- learning-rate schedules -------------------------------------------------------------------------------------------------
     def _scheduled_optimizer(self):
@@ -1446,8 +1556,13 @@ class Solver:
                 raise NotImplementedError(message)
         self.lrs.append(rate)
 
-    def _fit(self, niters, batch_size, sampler, loss_terms, optimizer, criterion, lr, lr_scheduler=None, lr_scheduler_kwargs=None, **kwargs):
+    def _fit(self, niters, batch_size, sampler, loss_terms, optimizer, criterion, lr, lr_scheduler=None, lr_scheduler_kwargs=None,
+             loss_weights=None, **kwargs):
         model = self.model
+        balance = None
+        if loss_weights is not None:            # (refusals first: the call has changed nothing yet)
+            balance = self._resolve_loss_weights(loss_weights, loss_terms if isinstance(loss_terms, (tuple, list)) else (loss_terms, ),
+                                                 self._steps_by_closure(optimizer, lr, kwargs))
         for num in self._constraints_seen:          # variables an earlier fit call brought to life are trainable now
             model.dormant_variables -= self._born_in_constraint.get(num, set())
         if optimizer is not None:                                                          # :419-422
@@ -1470,11 +1585,12 @@ class Solver:
         nums_constraints = [int(term.replace('constraint', '').replace('_', ''))
                             for term in loss_terms if 'constraint' in term]
         self._refresh_traces(set(nums_constraints))
-        if isinstance(self.optimizer, TorchOptimizerAdapter) or model.variables or not isinstance(self.optimizer, FlatAdam):
+        if isinstance(self.optimizer, TorchOptimizerAdapter) or model.variables or not isinstance(self.optimizer, FlatAdam) or balance is not None:
             # (what the terms of THIS call reach decides what torch's optimizers do with a parameter: one dry evaluation per fit call, asked
             #  for graph connectivity -- _unreached_scalars. Plain Adam on a model without variables need not know: nothing changes from call
             #  to call there, and its update of an entry that never has a gradient is no move at all; weight decay would move it, and a
             #  variable's reach differs from call to call, so every other case asks)
+            # (loss weights: an entry no term reaches is not a live entry of the statistics -- mean|g| divides by the live count)
             unreached = self._unreached_scalars(loss_terms, nums_constraints, criterion)
             self.optimizer.refresh(unreached)
             if optimizer is None and isinstance(self.optimizer, FlatOptimizer):
@@ -1485,6 +1601,7 @@ class Solver:
                     self.optimizer = TorchOptimizerAdapter.continuing(self.optimizer)
                     self.optimizer.refresh(unreached)
         else:
+            unreached = ()
             self.optimizer.refresh()
         self._constraints_seen |= {num for num in nums_constraints if num < len(self.constraints)}
         crit = self._lower_criterion(criterion)          # None: not lowerable (generic path)
@@ -1516,17 +1633,36 @@ class Solver:
         flat_adam = isinstance(self.optimizer, FlatOptimizer)       # (any rule of the kernels; FlatAdam is the default one)
         self.last_fit_optimizer = f"{self.optimizer.name}/{'fused' if flat_adam else 'torch'}"
         # (an optimizer that steps through a closure -- L-BFGS -- re-evaluates the batch: no fit chunks, launch graphs or one-launch form)
-        one_launch = fused and world == 1 and flat_adam and tuple(loss_terms) == ('equation',) and not self.optimizer.needs_closure
+        one_launch = (fused and world == 1 and flat_adam and tuple(loss_terms) == ('equation',) and not self.optimizer.needs_closure
+                      and balance is None)            # (a fit with weights takes the per-iteration path, also for the equation alone)
         stream = engine.stream_of(model.flat)           # looked up once per call, not per iteration
         history_ptr = history.data_ptr()
+        self.last_fit_balance, wb = None, None
+        if balance is not None:
+            terms = tuple(loss_terms)
+            balance.bind(model.net, terms, self.grads.numel(), self.device)
+            if flat_adam:
+                mask = self.optimizer.mask
+            else:                                       # (torch.optim steps the parameter views: the same entries -- trainable, reached -- are live)
+                mask = model.trainable_mask()
+                for off in unreached:
+                    mask[off] = 0
+            term_hist = torch.zeros((niters, len(terms)), dtype=torch.float32, device=self.device)
+            weight_hist = torch.zeros((niters, len(terms)), dtype=torch.float32, device=self.device)
+            self._term_pending.append((terms, term_hist, weight_hist, done))
+            self._balance = balance
+            self.last_fit_balance = f'{balance.kind}/{self.last_fit_path}'
+            wb = dict(balance=balance, rows=self._term_rows(len(terms)), mask=mask, term_ptr=term_hist.data_ptr(), weight_ptr=weight_hist.data_ptr(),
+                      nums=[None if term == 'equation' else int(term.replace('constraint', '').replace('_', '')) for term in terms],
+                      keep=(term_hist, weight_hist))
         try:
             self._fit_loop(niters, local_batch, sampler, loss_terms, nums_constraints, criterion, world, fused, one_launch,
-                           flat_adam, stream, history, history_ptr, done)
+                           flat_adam, stream, history, history_ptr, done, wb)
         finally:
             self._global_batch = None
 
     def _fit_loop(self, niters, local_batch, sampler, loss_terms, nums_constraints, criterion, world, fused, one_launch,
-                  flat_adam, stream, history, history_ptr, done):
+                  flat_adam, stream, history, history_ptr, done, wb=None):
         lay = self.model.net.layout
         columns = self._device_columns(sampler) if one_launch else None
         if columns is not None and not self._needs_ic_streams():
@@ -1540,7 +1676,14 @@ class Solver:
             if by_closure:
                 # the batch is drawn ONCE; every closure call re-runs the gradient part of the iteration on it, and the iteration's loss is
                 # what `step(closure)` returns: the loss at its first evaluation (`loss = opt.step(closure)`)
-                def closure(xs=xs):
+                recorded = []
+
+                def closure(xs=xs, it=it, recorded=recorded):
+                    if wb is not None:
+                        # (constant weights: the same rows + combine in every evaluation; the histories take the first one's, as `losses` does)
+                        self._weighted_step(xs, loss_terms, criterion, world, fused, wb, it=None if recorded else it, stream=stream)
+                        recorded.append(it)
+                        return
                     if fused:
                         self._fused_terms_step(xs, loss_terms, nums_constraints, world, stream=stream)
                     else:
@@ -1558,13 +1701,15 @@ class Solver:
                 done[0] = it + 1
                 self._rate_end(rate)
                 continue
-            if fused:
+            if wb is not None:
+                self._weighted_step(xs, loss_terms, criterion, world, fused, wb, it=it, stream=stream)
+            elif fused:
                 # (two to four launches per iteration: replaying them as a launch graph measured 0.048 -> 0.046 ms/it at batch 500 and
                 #  0.072 -> 0.081 at 65 536 -- the eager loop stays)
                 self._fused_terms_step(xs, loss_terms, nums_constraints, world, stream=stream)
             else:
                 self._generic_step_auto(xs, loss_terms, nums_constraints, criterion, world, remaining=niters - it)
-            if world > 1:
+            if world > 1 and wb is None:
                 self._all_reduce(stream)                # flat [p_total]: network, log_scale, loss slot, V slots
             if flat_adam:
                 self.optimizer.step(self.grads, loss_out=history_ptr + 4 * it, stream=stream)
