@@ -178,8 +178,8 @@ typedef struct pinn_residual {
      * the arithmetic the library had before these fields existed, bit for bit.
      *   criterion   PINN_CRIT_MSE / _L1 / _SMOOTH_L1 / _HUBER; anything else is refused
      *   crit_param  beta of nn.SmoothL1Loss (>= 0; 0 is L1, as in torch), delta of nn.HuberLoss (> 0, else refused); ignored by MSE / L1
-     *   crit_sum    != 0: reduction='sum'. The entry points that derive the scale from n_points themselves (pinn_residual_adam_step,
-     *               pinn_fit_steps, pinn_fit_steps_graph) then use 1 instead of 1 / n_points; pinn_residual_step / _step_add take the scale
+     *   crit_sum    != 0: reduction='sum'. The entry points that derive the scale from n_points themselves (pinn_residual_optim_step,
+     *               pinn_fit_steps) then use 1 instead of 1 / n_points; pinn_residual_step / _step_add take the scale
      *               from their caller in either case (`inv_n_global`: 1 for a sum, 1 / world for a term every data-parallel rank evaluates).
      * Non-MSE criteria run on the general tile kernels and on the residual-program kernels; the shape-specialised affine instantiations are
      * compiled for MSE alone, and a call with another criterion takes the general kernel of the same stream shape. */
@@ -274,32 +274,6 @@ int pinn_residual_step_add(pinn_t* net, const pinn_residual_t* residual, const f
                            float ic_const, float inv_n_global, float* grads, void* workspace, size_t workspace_bytes,
                            void* stream);
 
-/* Single-rank form of one whole `fit` iteration (model_torch.py:437-461): pinn_residual_step with inv_n = 1/n_points and
- * the Adam update of pinn_adam_step fused into the gradient-reduction launch (no all-reduce can sit in between, so
- * data-parallel ranks use the two separate calls). `step` is the 1-based Adam step of THIS update; it is also stored
- * to step_ptr[0] so that the two forms can be mixed. grads still receives the gradient and the loss slot; loss_out
- * (nullable) is one more device address that receives the loss -- the host points it at entry i of its loss history
- * (`self.losses.append(...)`, model_torch.py:464) so that recording an iteration costs no launch and no synchronisation. */
-int pinn_residual_adam_step(pinn_t* net, const pinn_residual_t* residual, float* params, const float* xs,
-                            int64_t n_points, const int* dir_cols, int nd, int n2, const float* ic_streams,
-                            float ic_const, float* grads, float* exp_avg, float* exp_avg_sq, const uint8_t* mask,
-                            int32_t* step_ptr, int32_t step, float lr, float beta1, float beta2, float eps,
-                            float* loss_out, void* workspace, size_t workspace_bytes, void* stream);
-
-/* torch.optim.Adam.step (model_torch.py:461; defaults beta=(0.9,0.999), eps=1e-8, no weight decay) on the flat
- * buffer.  mask[i]==0 freezes entry i (padding, frozen layers/variables: model_torch.py:56-105, :420-421).
- * `step` is the 1-based step count read from device memory (step_ptr[0], int32) so that the call can be
- * replayed from a hipGraph; the kernel increments it. */
-int pinn_adam_step(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, const uint8_t* mask,
-                   int64_t n, int32_t* step_ptr, float lr, float beta1, float beta2, float eps, void* stream);
-/* Same update with the 1-based step passed by value (the host counts, as torch.optim does): ONE launch instead of
- * two; the value is also stored to step_ptr[0] so that the forms can be mixed. Data-parallel ranks call this after the
- * gradient all-reduce; loss_out (nullable) then receives grads[off_loss] -- the all-reduced loss of the iteration goes
- * straight into entry i of the host's loss history (`self.losses.append(...)`, model_torch.py:464) in the same launch. */
-int pinn_adam_step_at(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, const uint8_t* mask,
-                      int64_t n, int32_t* step_ptr, int32_t step, float lr, float beta1, float beta2, float eps,
-                      float* loss_out, int32_t off_loss, void* stream);
-
 /* The update rule of the optimizer entry points below: the `_single_tensor_*` arithmetic of torch.optim.{Adam, AdamW, SGD, RMSprop}
  * (the optimizer `Solver.fit(optimizer=...)` names, model_torch.py:420-422, :461) on the flat buffer. At most TWO state arrays per rule, the
  * `exp_avg` / `exp_avg_sq` arguments of the entry points:
@@ -309,13 +283,14 @@ int pinn_adam_step_at(float* params, const float* grads, float* exp_avg, float* 
  *   PINN_OPT_SGD       SGD(lr, momentum, dampening, nesterov, weight_decay)    momentum_buffer      (untouched)
  *   PINN_OPT_RMSPROP   RMSprop(lr, alpha, eps, weight_decay, momentum,         momentum_buffer or   square_avg
  *                              centered)                                       grad_avg
- * Adam: weight_decay != 0 adds weight_decay * p to the gradient in front; weight_decay == 0 is the arithmetic of pinn_adam_step, bit for bit.
+ * Adam: weight_decay != 0 adds weight_decay * p to the gradient in front; weight_decay == 0 is torch.optim.Adam.step as the reference
+ * calls it (model_torch.py:461; torch's defaults are betas (0.9, 0.999), eps 1e-8).
  * AdamW: p *= 1 - lr * weight_decay in front of the Adam step (decoupled). SGD: the update of step 1 SETS the momentum buffer to the gradient
  * (no 1 - dampening), as torch does for a parameter without a buffer; nesterov needs momentum > 0 and dampening == 0 (torch's own check).
- * RMSprop: momentum > 0 together with centered would need three arrays and is refused. An entry with mask[i] == 0 keeps value AND state: it
- * is not decayed either. A struct with `rule` and the fields behind `eps` zero and Adam's four numbers filled is plain Adam. Refused (non-zero,
- * pinn_last_error, nothing launched): an unknown rule, negative lr / eps / weight_decay / momentum / alpha, betas outside [0, 1), the
- * combinations named above. */
+ * RMSprop: momentum > 0 together with centered would need three arrays and is refused. An entry with mask[i] == 0 (padding, frozen layers /
+ * variables: model_torch.py:56-105, :420-421) keeps value AND state: it is not decayed either. A struct with `rule` and the fields behind
+ * `eps` zero and Adam's four numbers filled is plain Adam. Refused (non-zero, pinn_last_error, nothing launched): an unknown rule, negative
+ * lr / eps / weight_decay / momentum / alpha, betas outside [0, 1), the combinations named above. */
 #define PINN_OPT_ADAM    0
 #define PINN_OPT_ADAMW   1
 #define PINN_OPT_SGD     2
@@ -327,9 +302,14 @@ typedef struct pinn_optim {
     int nesterov, centered;
 } pinn_optim_t;
 
-/* pinn_adam_step / pinn_adam_step_at with the rule of `opt`: step <= 0 counts on the device (step_ptr[0] is incremented and read), step >= 1
- * is the host's 1-based count (mirrored to step_ptr[0]; loss_out / off_loss as in pinn_adam_step_at). The step count is the optimizer's: SGD
- * takes "step 1" for "no momentum buffer yet". */
+/* One update of the flat buffer with the rule of `opt`. The step count is the optimizer's (1-based; SGD takes "step 1" for "no momentum
+ * buffer yet") and lives in device memory, step_ptr[0] (int32).
+ * pinn_optim_step counts on the device: a launch of its own increments step_ptr[0] and the update reads it, so that the call can be
+ * replayed from a hipGraph.
+ * pinn_optim_step_at takes the host's count `step` >= 1 by value (the host counts, as torch.optim does): ONE launch instead of two; the
+ * value is also stored to step_ptr[0] so that the forms can be mixed. Data-parallel ranks call it after the gradient all-reduce; loss_out
+ * (nullable) then receives grads[off_loss] -- the all-reduced loss of the iteration goes straight into entry i of the host's loss history
+ * (`self.losses.append(...)`, model_torch.py:464) in the same launch. */
 int pinn_optim_step(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, const uint8_t* mask, int64_t n,
                     int32_t* step_ptr, const pinn_optim_t* opt, void* stream);
 int pinn_optim_step_at(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, const uint8_t* mask, int64_t n,
@@ -341,64 +321,54 @@ int pinn_optim_step_at(float* params, const float* grads, float* exp_avg, float*
 int pinn_reduce_rows(const float* partials, int32_t n_rows, int32_t row_len, float* grads, int accumulate, float* params, float* exp_avg,
                      float* exp_avg_sq, const uint8_t* mask, int32_t* step_ptr, int32_t step, const pinn_optim_t* opt, float* loss_out,
                      int32_t off_loss, void* stream);
-/* pinn_residual_adam_step, pinn_fit_steps and pinn_fit_steps_graph with the rule of `opt` (the Adam entry points are these with a plain-Adam
- * struct). The launch-graph cache of pinn_fit_steps_optim_graph keys on the whole struct. */
+/* Single-rank form of one whole `fit` iteration (model_torch.py:437-461): pinn_residual_step with inv_n = 1/n_points and the update of
+ * pinn_optim_step_at fused into the gradient-reduction launch (no all-reduce can sit in between, so data-parallel ranks use the two
+ * separate calls). `step` is the 1-based step of THIS update; it is also stored to step_ptr[0]. grads still receives the gradient and the
+ * loss slot; loss_out (nullable) is one more device address that receives the loss -- the host points it at entry i of its loss history
+ * so that recording an iteration costs no launch and no synchronisation. */
 int pinn_residual_optim_step(pinn_t* net, const pinn_residual_t* residual, float* params, const float* xs,
                              int64_t n_points, const int* dir_cols, int nd, int n2, const float* ic_streams,
                              float ic_const, float* grads, float* exp_avg, float* exp_avg_sq, const uint8_t* mask,
                              int32_t* step_ptr, int32_t step, const pinn_optim_t* opt, float* loss_out, void* workspace,
                              size_t workspace_bytes, void* stream);
-int pinn_fit_steps_optim(pinn_t* net, const pinn_residual_t* residual, float* params, float* xs, int64_t n_points,
-                         const int* kind, const float* a, const float* b, uint64_t seed, uint64_t call_index0,
-                         const int* dir_cols, int nd, int n2, float ic_const, float* grads, float* exp_avg, float* exp_avg_sq,
-                         const uint8_t* mask, int32_t* step_ptr, int32_t step0, const pinn_optim_t* opt,
-                         float* loss_history, int32_t k_steps, void* workspace, size_t workspace_bytes, void* stream);
-int pinn_fit_steps_optim_graph(pinn_t* net, const pinn_residual_t* residual, float* params, float* xs, int64_t n_points,
-                               const int* kind, const float* a, const float* b, uint64_t seed, uint64_t call_index0,
-                               const int* dir_cols, int nd, int n2, float ic_const, float* grads, float* exp_avg, float* exp_avg_sq,
-                               const uint8_t* mask, int32_t* step_ptr, int32_t step0, const pinn_optim_t* opt,
-                               float* loss_history, int32_t k_steps, void* workspace, size_t workspace_bytes, void* ctrl,
-                               size_t ctrl_bytes, void* stream);
-/* pinn_fit_steps_optim_graph under a learning-rate schedule (`torch.optim.lr_scheduler`: the loop `opt.step(); sched.step()` around
- * model_torch.py:461). lr_steps is HOST memory, k_steps finite rates >= 0 that the caller's scheduler produced: iteration k of the chunk
- * is the update pinn_residual_optim_step performs with opt->lr = lr_steps[k] -- bit for bit on the eager loop and on the launch-graph form;
- * on the one-launch form of narrow nets within the bound that form has against the eager loop. The rates reach the kernels through the
- * control block, per iteration like Adam's bias corrections (step_size[k] from lr_steps[k]; lr[k] for SGD and RMSprop; decay[k] =
- * 1 - lr_steps[k] * weight_decay for AdamW, formed in double from the decimal values like every other derived scalar). The launch-graph
- * cache key of a call with lr_steps leaves opt->lr out: chunks that differ only in their rates replay one recording. opt->lr itself must
- * still be valid; it is used nowhere. lr_steps == NULL is pinn_fit_steps_optim_graph. The array is read before the call returns. */
-int pinn_fit_steps_optim_sched(pinn_t* net, const pinn_residual_t* residual, float* params, float* xs, int64_t n_points,
-                               const int* kind, const float* a, const float* b, uint64_t seed, uint64_t call_index0,
-                               const int* dir_cols, int nd, int n2, float ic_const, float* grads, float* exp_avg, float* exp_avg_sq,
-                               const uint8_t* mask, int32_t* step_ptr, int32_t step0, const pinn_optim_t* opt,
-                               float* loss_history, int32_t k_steps, void* workspace, size_t workspace_bytes, void* ctrl,
-                               size_t ctrl_bytes, void* stream, const float* lr_steps);
 
-/* The reference's fit loop (model_torch.py:426-464) for the common case -- on-device column sampler, one equation term on the
- * fused path, Adam -- as ONE call that enqueues `k_steps` iterations: iteration k draws batch `call_index0 + k` into `xs`
- * (pinn_sample_points with kind / a / b / seed), runs pinn_residual_adam_step with Adam step `step0 + k` and leaves the
- * iteration's loss in loss_history[k] (device memory). Asynchronous like every entry point; at 100-point batches the host
- * loop is what bounds Solver.fit (three launches per iteration), and this keeps it out of the interpreter. Problems with
- * ic_streams (an initial condition the tracer could not lower) do not take this path. */
+/* The reference's fit loop (model_torch.py:426-464) for the common case -- on-device column sampler, one equation term on the fused path,
+ * a rule of pinn_optim_t -- as ONE call that enqueues `k_steps` iterations: iteration k draws batch `call_index0 + k` into `xs`
+ * (pinn_sample_points with kind / a / b / seed), runs pinn_residual_optim_step with step `step0 + k` and leaves the iteration's loss in
+ * loss_history[k] (device memory). Asynchronous like every entry point; at 100-point batches the host loop is what bounds Solver.fit
+ * (three launches per iteration), and this keeps it out of the interpreter. Problems with ic_streams (an initial condition the tracer
+ * could not lower) do not take this path.
+ *   sampler    from the second iteration on the batch is drawn by the reduction launch of the iteration before (the tile kernel of that
+ *              iteration is through with the buffer): one dependent launch less per iteration wherever the step is one pass. `xs` holds
+ *              the batch of the last iteration afterwards.
+ *   ctrl       NULL: the eager loop, every launch of every iteration enqueued on `stream`. Otherwise a caller-owned device buffer of at least
+ *              pinn_fit_ctrl_bytes() bytes: what changes from iteration to iteration (Philox batch counter, step and its bias corrections,
+ *              learning rate, slot of the loss history) is written there by an ordinary launch in front of the chunk, and the kernels read
+ *              it at the iteration number they carry. With it the chunk runs in the first form below that applies.
+ *   one launch a NARROW net (hidden width <= 32), 1 <= k_steps <= 128, a batch of few tiles (pinn_debug_fit_persistent): the whole chunk
+ *              is one kernel. Same batches; updates and losses follow the eager loop to fp32 round-off, not bit for bit.
+ *   graph      k_steps == 128 (one whole chunk of Solver.fit): the chunk as ONE replayable launch graph (hipGraph) -- for batches of a
+ *              few thousand points the gaps between the dependent launches of an iteration are a visible share of it. The first chunk of
+ *              a configuration runs eagerly and is captured; later chunks with the same arguments (net, residual, buffers, sizes,
+ *              sampler columns, the whole of `opt`; not seed, call_index0, step0) replay. Same batches, updates and loss history as the
+ *              eager loop, bit for bit.
+ *   otherwise  (another k_steps, profiling on, capture refused by the runtime) the eager loop.
+ *   lr_steps   NULL: the constant rate opt->lr. Otherwise a learning-rate schedule (`torch.optim.lr_scheduler`: the loop `opt.step();
+ *              sched.step()` around model_torch.py:461): HOST memory, k_steps finite rates >= 0 that the caller's scheduler produced, read
+ *              before the call returns. Iteration k is the update pinn_residual_optim_step performs with opt->lr = lr_steps[k] -- bit for
+ *              bit on the eager loop and on the launch-graph form; on the one-launch form within the bound that form has against the
+ *              eager loop. The rates reach the kernels through the control block, per iteration like Adam's bias corrections
+ *              (step_size[k] from lr_steps[k]; lr[k] for SGD and RMSprop; decay[k] = 1 - lr_steps[k] * weight_decay for AdamW, formed in
+ *              double from the decimal values like every other derived scalar). The launch-graph cache key of a call with lr_steps
+ *              leaves opt->lr out: chunks that differ only in their rates replay one recording. opt->lr itself must still be valid; it
+ *              is used nowhere. */
+size_t pinn_fit_ctrl_bytes(void);
 int pinn_fit_steps(pinn_t* net, const pinn_residual_t* residual, float* params, float* xs, int64_t n_points,
                    const int* kind, const float* a, const float* b, uint64_t seed, uint64_t call_index0,
                    const int* dir_cols, int nd, int n2, float ic_const, float* grads, float* exp_avg, float* exp_avg_sq,
-                   const uint8_t* mask, int32_t* step_ptr, int32_t step0, float lr, float beta1, float beta2, float eps,
-                   float* loss_history, int32_t k_steps, void* workspace, size_t workspace_bytes, void* stream);
-/* The same chunk as ONE replayable launch graph (hipGraph): for batches of a few thousand points the gaps between the three dependent
- * launches of an iteration are a visible share of it. What changes from iteration to iteration (Philox batch counter, Adam step and its
- * bias corrections, slot of the loss history) is read by the kernels from `ctrl` -- a caller-owned device buffer of at least
- * pinn_fit_ctrl_bytes() bytes, rewritten by an ordinary launch in front of every replay -- indexed by the iteration number baked into the
- * graph's nodes. The first chunk of a configuration runs eagerly and captures; later chunks with the same arguments replay; anything that
- * does not qualify (k_steps != 128 = one whole chunk of Solver.fit, profiling on, capture refused) runs pinn_fit_steps. Same batches, updates and loss history as
- * the eager loop, bit for bit. */
-size_t pinn_fit_ctrl_bytes(void);
-int pinn_fit_steps_graph(pinn_t* net, const pinn_residual_t* residual, float* params, float* xs, int64_t n_points,
-                         const int* kind, const float* a, const float* b, uint64_t seed, uint64_t call_index0,
-                         const int* dir_cols, int nd, int n2, float ic_const, float* grads, float* exp_avg, float* exp_avg_sq,
-                         const uint8_t* mask, int32_t* step_ptr, int32_t step0, float lr, float beta1, float beta2, float eps,
-                         float* loss_history, int32_t k_steps, void* workspace, size_t workspace_bytes, void* ctrl,
-                         size_t ctrl_bytes, void* stream);
+                   const uint8_t* mask, int32_t* step_ptr, int32_t step0, const pinn_optim_t* opt,
+                   float* loss_history, int32_t k_steps, void* workspace, size_t workspace_bytes, void* ctrl,
+                   size_t ctrl_bytes, void* stream, const float* lr_steps);
 
 /* tanh of the hidden layers (round 5). PINN_TANH_FAST (default): sign(z)(1 - t)/(1 + t), t = e^{-2|z|} -- absolute error 1.5e-7, relative
  * accuracy lost to cancellation below |z| ~ 0.3. PINN_TANH_ACCURATE: z P(z^2) below |z| = 0.45 (degree-4 minimax fit, 1.5e-7 RELATIVE); on
@@ -456,7 +426,7 @@ int pinn_debug_wgx_chunk_bytes(pinn_t* net, long long bytes);
  *                                 restores the default, 4): tests run the same step at 1 and at several workgroups per CU; affects
  *                                 pinn_workspace_bytes (partial rows, slabs), so set it first. Returns the previous bound (-1: null). */
 int pinn_debug_max_wgs_per_cu(pinn_t* net, int cap);
-/*   pinn_debug_fit_persistent     how pinn_fit_steps_graph runs a chunk of a NARROW net (hidden width <= 32) as ONE launch (pinn_fit_kernel.h):
+/*   pinn_debug_fit_persistent     how pinn_fit_steps (with a control block) runs a chunk of a NARROW net (hidden width <= 32) as ONE launch (pinn_fit_kernel.h):
  *                                 2 (default): the one-CU form -- one hardware workgroup of up to eight virtual workgroups with parameters, Adam
  *                                   state, partial rows and batch resident in LDS; the iteration's only synchronisation is a workgroup
  *                                   barrier -- for batches of at most `rounds` sweeps of those virtual workgroups (pinn_debug_fit_onecu_rounds,

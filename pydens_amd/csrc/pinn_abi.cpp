@@ -90,7 +90,7 @@ struct pinn_net {
     int n_cu;
     int gemm_mode;                  // PINN_GEMM_FP32 / PINN_GEMM_BF16X3 (pinn_set_gemm_mode)
     int tanh_mode;                  // PINN_TANH_FAST / PINN_TANH_ACCURATE (pinn_set_tanh_mode)
-    // pinn_fit_steps_graph: the instantiated launch graph of one chunk and the arguments it was captured with (host state of the
+    // pinn_fit_steps: the instantiated launch graph of one chunk and the arguments it was captured with (host state of the
     // descriptor; no device memory: the control block is the caller's)
     void* fit_graph_exec;
     unsigned long long fit_graph_key[4];
@@ -437,7 +437,7 @@ static PinnOptK optim_at_rate(const PinnOptK& k, float lr) {
     return r;
 }
 
-// lr_steps of pinn_fit_steps_optim_sched: k_steps finite, non-negative rates in host memory (NULL: the constant rate of the struct)
+// lr_steps of pinn_fit_steps: k_steps finite, non-negative rates in host memory (NULL: the constant rate of the struct)
 static int check_lr_steps(const float* lr_steps, int32_t k_steps) {
     for (int32_t k = 0; lr_steps && k < k_steps; ++k)
         if (!(lr_steps[k] >= 0.0f) || !(lr_steps[k] <= FLT_MAX)) return fail("lr_steps[%d]: invalid learning rate %g", (int)k, (double)lr_steps[k]);
@@ -1165,24 +1165,13 @@ int pinn_residual_step_add(pinn_t* net, const pinn_residual_t* residual, const f
     return residual_step_impl(c, inv_n_global, nullptr, 1);
 }
 
-// one whole iteration with the update of `tail` in the last reduction launch (the Adam entry points hand in plain_adam(...): Adam's four
-// numbers travel as they always did, unchecked; the family's entry points go through optim_prepare first)
+// one whole iteration with the update of `tail` in the last reduction launch (the rule has been through optim_prepare)
 static int residual_optim_step(const StepCall& c, StepTail* tail) {
     if (!c.net || !tail->m || !tail->v || !tail->step_ptr) return fail("null argument");
     if (tail->step_value < 1) return fail("step must be >= 1");
     tail->off_loss = c.net->lay.off_loss;
     // (reduction='sum', pinn_residual_t::crit_sum: no division by the number of points)
     return residual_step_impl(c, (c.residual && c.residual->crit_sum) ? 1.0f : 1.0f / (float)c.n_points, tail);
-}
-
-int pinn_residual_adam_step(pinn_t* net, const pinn_residual_t* residual, float* params, const float* xs,
-                            int64_t n_points, const int* dir_cols, int nd, int n2, const float* ic_streams,
-                            float ic_const, float* grads, float* exp_avg, float* exp_avg_sq, const uint8_t* mask,
-                            int32_t* step_ptr, int32_t step, float lr, float beta1, float beta2, float eps,
-                            float* loss_out, void* workspace, size_t workspace_bytes, void* stream) {
-    const StepCall c = {net, residual, params, xs, n_points, dir_cols, nd, n2, ic_streams, ic_const, grads, workspace, workspace_bytes, stream};
-    StepTail tail = update_tail({params, exp_avg, exp_avg_sq, mask, step_ptr}, step, plain_adam(lr, beta1, beta2, eps), loss_out);
-    return residual_optim_step(c, &tail);
 }
 
 int pinn_residual_optim_step(pinn_t* net, const pinn_residual_t* residual, float* params, const float* xs,
@@ -1247,37 +1236,8 @@ static int enqueue_chunk(const FitCall& f, void* stream, const PinnFitCtrl* capt
     return rc;
 }
 
-static int fit_steps_eager(const FitCall& f) {
-    if (!f.step.net || !f.xs || !f.loss_history) return fail("null argument");
-    if (f.k_steps < 0 || f.step0 < 1) return fail("k_steps must be >= 0 and step0 >= 1");
-    if (check_lr_steps(f.lr_steps, f.k_steps)) return 1;
-    return enqueue_chunk(f, f.step.stream, nullptr);
-}
-
-// the record of a pinn_fit_steps* call from the parameter names all five entry points share; what differs between them comes as arguments
-#define PINN_FIT_CALL(optk, ctrl_, ctrl_bytes_, lr_steps_)                                                                                   \
-    {{net, residual, params, xs, n_points, dir_cols, nd, n2, nullptr, ic_const, grads, workspace, workspace_bytes, stream},                   \
-     xs, kind, a, b, seed, call_index0, {params, exp_avg, exp_avg_sq, mask, step_ptr}, step0, optk, loss_history, k_steps, ctrl_, ctrl_bytes_, lr_steps_}
-
-int pinn_fit_steps(pinn_t* net, const pinn_residual_t* residual, float* params, float* xs, int64_t n_points,
-                   const int* kind, const float* a, const float* b, uint64_t seed, uint64_t call_index0,
-                   const int* dir_cols, int nd, int n2, float ic_const, float* grads, float* exp_avg, float* exp_avg_sq,
-                   const uint8_t* mask, int32_t* step_ptr, int32_t step0, float lr, float beta1, float beta2, float eps,
-                   float* loss_history, int32_t k_steps, void* workspace, size_t workspace_bytes, void* stream) {
-    const FitCall f = PINN_FIT_CALL(plain_adam(lr, beta1, beta2, eps), nullptr, 0, nullptr);
-    return fit_steps_eager(f);
-}
-
-int pinn_fit_steps_optim(pinn_t* net, const pinn_residual_t* residual, float* params, float* xs, int64_t n_points,
-                         const int* kind, const float* a, const float* b, uint64_t seed, uint64_t call_index0,
-                         const int* dir_cols, int nd, int n2, float ic_const, float* grads, float* exp_avg, float* exp_avg_sq,
-                         const uint8_t* mask, int32_t* step_ptr, int32_t step0, const pinn_optim_t* opt,
-                         float* loss_history, int32_t k_steps, void* workspace, size_t workspace_bytes, void* stream) {
-    PinnOptK k;
-    if (optim_prepare(opt, &k)) return 1;
-    const FitCall f = PINN_FIT_CALL(k, nullptr, 0, nullptr);
-    return fit_steps_eager(f);
-}
+// the eager loop: the chunk without a control block, and the fallback of the other forms (pinn_fit_steps has checked the arguments)
+static int fit_steps_eager(const FitCall& f) { return enqueue_chunk(f, f.step.stream, nullptr); }
 
 size_t pinn_fit_ctrl_bytes(void) { return sizeof(PinnFitCtrl); }
 
@@ -1409,10 +1369,23 @@ static int replay_chunk(const FitCall& f) {
 }
 #endif
 
-static int fit_steps_graph_impl(const FitCall& f) {
-    if (!f.step.net || !f.step.residual || !f.xs || !f.loss_history || !f.kind || !f.a || !f.b || !f.step.dir_cols) return fail("null argument");
-    if (f.k_steps < 0 || f.step0 < 1) return fail("k_steps must be >= 0 and step0 >= 1");
-    if (check_lr_steps(f.lr_steps, f.k_steps)) return 1;
+int pinn_fit_steps(pinn_t* net, const pinn_residual_t* residual, float* params, float* xs, int64_t n_points,
+                   const int* kind, const float* a, const float* b, uint64_t seed, uint64_t call_index0,
+                   const int* dir_cols, int nd, int n2, float ic_const, float* grads, float* exp_avg, float* exp_avg_sq,
+                   const uint8_t* mask, int32_t* step_ptr, int32_t step0, const pinn_optim_t* opt,
+                   float* loss_history, int32_t k_steps, void* workspace, size_t workspace_bytes, void* ctrl,
+                   size_t ctrl_bytes, void* stream, const float* lr_steps) {
+    PinnOptK k;
+    if (optim_prepare(opt, &k)) return 1;
+    const FitCall f = {{net, residual, params, xs, n_points, dir_cols, nd, n2, nullptr, ic_const, grads, workspace, workspace_bytes, stream},
+                       xs, kind, a, b, seed, call_index0, {params, exp_avg, exp_avg_sq, mask, step_ptr}, step0, k, loss_history, k_steps,
+                       ctrl, ctrl_bytes, lr_steps};
+    if (!net || !xs || !loss_history) return fail("null argument");
+    // (without a control block the chunk is the eager loop alone, which reads dir_cols only for nd > 0 and, at k_steps == 0, nothing but
+    //  the three above: such calls are accepted as they always were)
+    if ((ctrl || k_steps != 0) && (!residual || !kind || !a || !b || (!dir_cols && (ctrl || nd > 0)))) return fail("null argument");
+    if (k_steps < 0 || step0 < 1) return fail("k_steps must be >= 0 and step0 >= 1");
+    if (check_lr_steps(lr_steps, k_steps)) return 1;
     bool launched = false;
     if (const int rc = try_one_launch_chunk(f, &launched)) return rc;
     if (launched) return 0;
@@ -1422,41 +1395,6 @@ static int fit_steps_graph_impl(const FitCall& f) {
     return replay_chunk(f);
 #endif
 }
-
-int pinn_fit_steps_graph(pinn_t* net, const pinn_residual_t* residual, float* params, float* xs, int64_t n_points,
-                         const int* kind, const float* a, const float* b, uint64_t seed, uint64_t call_index0,
-                         const int* dir_cols, int nd, int n2, float ic_const, float* grads, float* exp_avg, float* exp_avg_sq,
-                         const uint8_t* mask, int32_t* step_ptr, int32_t step0, float lr, float beta1, float beta2, float eps,
-                         float* loss_history, int32_t k_steps, void* workspace, size_t workspace_bytes, void* ctrl,
-                         size_t ctrl_bytes, void* stream) {
-    const FitCall f = PINN_FIT_CALL(plain_adam(lr, beta1, beta2, eps), ctrl, ctrl_bytes, nullptr);
-    return fit_steps_graph_impl(f);
-}
-
-int pinn_fit_steps_optim_graph(pinn_t* net, const pinn_residual_t* residual, float* params, float* xs, int64_t n_points,
-                               const int* kind, const float* a, const float* b, uint64_t seed, uint64_t call_index0,
-                               const int* dir_cols, int nd, int n2, float ic_const, float* grads, float* exp_avg, float* exp_avg_sq,
-                               const uint8_t* mask, int32_t* step_ptr, int32_t step0, const pinn_optim_t* opt,
-                               float* loss_history, int32_t k_steps, void* workspace, size_t workspace_bytes, void* ctrl,
-                               size_t ctrl_bytes, void* stream) {
-    PinnOptK k;
-    if (optim_prepare(opt, &k)) return 1;
-    const FitCall f = PINN_FIT_CALL(k, ctrl, ctrl_bytes, nullptr);
-    return fit_steps_graph_impl(f);
-}
-
-int pinn_fit_steps_optim_sched(pinn_t* net, const pinn_residual_t* residual, float* params, float* xs, int64_t n_points,
-                               const int* kind, const float* a, const float* b, uint64_t seed, uint64_t call_index0,
-                               const int* dir_cols, int nd, int n2, float ic_const, float* grads, float* exp_avg, float* exp_avg_sq,
-                               const uint8_t* mask, int32_t* step_ptr, int32_t step0, const pinn_optim_t* opt,
-                               float* loss_history, int32_t k_steps, void* workspace, size_t workspace_bytes, void* ctrl,
-                               size_t ctrl_bytes, void* stream, const float* lr_steps) {
-    PinnOptK k;
-    if (optim_prepare(opt, &k)) return 1;
-    const FitCall f = PINN_FIT_CALL(k, ctrl, ctrl_bytes, lr_steps);
-    return fit_steps_graph_impl(f);
-}
-#undef PINN_FIT_CALL
 
 static int optim_launch(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, const uint8_t* mask, int64_t n,
                         int32_t* step_ptr, int32_t step, const PinnOptK& opt, void* stream,
@@ -1469,20 +1407,6 @@ static int optim_launch(float* params, const float* grads, float* exp_avg, float
     if (step <= 0 && launch("optimizer kernel", pinn_tick_kernel, 1, 64, 0, stream, (int*)step_ptr)) return 1;
     return launch("optimizer kernel", pinn_optim_kernel, blocks, 256, 0, stream, params, grads, exp_avg, exp_avg_sq, mask, (long long)n,
                   (int*)step_ptr, (int)step, step_size, bc2_sqrt, opt, loss_out, off_loss);
-}
-
-int pinn_adam_step(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, const uint8_t* mask, int64_t n,
-                   int32_t* step_ptr, float lr, float beta1, float beta2, float eps, void* stream) {
-    return optim_launch(params, grads, exp_avg, exp_avg_sq, mask, n, step_ptr, 0, plain_adam(lr, beta1, beta2, eps), stream);
-}
-
-int pinn_adam_step_at(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, const uint8_t* mask, int64_t n,
-                      int32_t* step_ptr, int32_t step, float lr, float beta1, float beta2, float eps, float* loss_out,
-                      int32_t off_loss, void* stream) {
-    if (step < 1) return fail("step must be >= 1");
-    if (loss_out && (off_loss < 0 || off_loss >= n)) return fail("off_loss=%d outside the gradient buffer", off_loss);
-    return optim_launch(params, grads, exp_avg, exp_avg_sq, mask, n, step_ptr, step, plain_adam(lr, beta1, beta2, eps), stream, loss_out,
-                        off_loss);
 }
 
 int pinn_optim_step(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, const uint8_t* mask, int64_t n,

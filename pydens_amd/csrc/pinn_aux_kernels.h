@@ -188,7 +188,7 @@ struct PinnFitCtrl {
                                         // block, not baked into the graph's nodes, a recorded chunk survives across fit calls)
     float step_size[PINN_FIT_CHUNK_MAX], bc2_sqrt[PINN_FIT_CHUNK_MAX];      // pinn_adam_scalars per iteration (computed on the host in
                                                                              // double, as for the eager loop: bit-identical updates)
-    // the learning rate of every iteration (pinn_fit_steps_optim_sched; a constant rate fills both arrays with one value): lr[k] is what
+    // the learning rate of every iteration (lr_steps of pinn_fit_steps; a constant rate fills both arrays with one value): lr[k] is what
     // SGD and RMSprop multiply with, decay[k] AdamW's 1 - lr_k * weight_decay formed on the host like PinnOptK::decay; Adam's and AdamW's
     // rate is in step_size[k]. A recorded chunk reads all of them here, so it replays under any rate.
     float lr[PINN_FIT_CHUNK_MAX], decay[PINN_FIT_CHUNK_MAX];

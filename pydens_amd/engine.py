@@ -138,35 +138,20 @@ def bind(lib):
     lib.pinn_residual_step.argtypes = [vp, ctypes.POINTER(Residual), vp, vp, i64, ip, i32, i32, vp, f32, f32, vp, vp,
                                        ctypes.c_size_t, vp]
     lib.pinn_residual_step_add.argtypes = lib.pinn_residual_step.argtypes
-    lib.pinn_adam_step.argtypes = [vp, vp, vp, vp, vp, i64, vp, f32, f32, f32, f32, vp]
-    lib.pinn_adam_step_at.argtypes = [vp, vp, vp, vp, vp, i64, vp, i32, f32, f32, f32, f32, vp, i32, vp]
-    lib.pinn_residual_adam_step.argtypes = [vp, ctypes.POINTER(Residual), vp, vp, i64, ip, i32, i32, vp, f32, vp, vp, vp, vp,
-                                            vp, i32, f32, f32, f32, f32, vp, vp, ctypes.c_size_t, vp]
     lib.pinn_sample_points.argtypes = [vp, i64, i32, ip, ctypes.POINTER(f32), ctypes.POINTER(f32), ctypes.c_uint64,
                                        ctypes.c_uint64, vp]
-    lib.pinn_fit_steps.argtypes = [vp, ctypes.POINTER(Residual), vp, vp, i64, ip, ctypes.POINTER(f32), ctypes.POINTER(f32),
-                                   ctypes.c_uint64, ctypes.c_uint64, ip, i32, i32, f32, vp, vp, vp, vp, vp, i32, f32, f32, f32, f32,
-                                   vp, i32, vp, ctypes.c_size_t, vp]
-    lib.pinn_fit_steps.restype = i32
-    lib.pinn_fit_steps_graph.argtypes = [vp, ctypes.POINTER(Residual), vp, vp, i64, ip, ctypes.POINTER(f32), ctypes.POINTER(f32),
-                                         ctypes.c_uint64, ctypes.c_uint64, ip, i32, i32, f32, vp, vp, vp, vp, vp, i32, f32, f32, f32, f32,
-                                         vp, i32, vp, ctypes.c_size_t, vp, ctypes.c_size_t, vp]
-    lib.pinn_fit_steps_graph.restype = i32
     lib.pinn_fit_ctrl_bytes.restype = ctypes.c_size_t
-    # the optimizer family: the Adam entry points with `const pinn_optim_t*` in place of (lr, beta1, beta2, eps)
+    # the optimizer family: the rule travels as `const pinn_optim_t*`
     op = ctypes.POINTER(Optim)
     lib.pinn_optim_step.argtypes = [vp, vp, vp, vp, vp, i64, vp, op, vp]
     lib.pinn_optim_step_at.argtypes = [vp, vp, vp, vp, vp, i64, vp, i32, op, vp, i32, vp]
     lib.pinn_residual_optim_step.argtypes = [vp, ctypes.POINTER(Residual), vp, vp, i64, ip, i32, i32, vp, f32, vp, vp, vp, vp,
                                              vp, i32, op, vp, vp, ctypes.c_size_t, vp]
-    lib.pinn_fit_steps_optim.argtypes = [vp, ctypes.POINTER(Residual), vp, vp, i64, ip, ctypes.POINTER(f32), ctypes.POINTER(f32),
-                                         ctypes.c_uint64, ctypes.c_uint64, ip, i32, i32, f32, vp, vp, vp, vp, vp, i32, op,
-                                         vp, i32, vp, ctypes.c_size_t, vp]
-    lib.pinn_fit_steps_optim_graph.argtypes = lib.pinn_fit_steps_optim.argtypes[:-1] + [vp, ctypes.c_size_t, vp]
-    # ... and the launch-graph form under a learning-rate schedule: one more argument, the k_steps rates in host memory
-    lib.pinn_fit_steps_optim_sched.argtypes = lib.pinn_fit_steps_optim_graph.argtypes + [ctypes.POINTER(f32)]
-    for name in ('pinn_optim_step', 'pinn_optim_step_at', 'pinn_residual_optim_step', 'pinn_fit_steps_optim', 'pinn_fit_steps_optim_graph',
-                 'pinn_fit_steps_optim_sched'):
+    # (... workspace, ctrl, ctrl_bytes, stream, lr_steps: the control block may be NULL, the k_steps rates are host memory or NULL)
+    lib.pinn_fit_steps.argtypes = [vp, ctypes.POINTER(Residual), vp, vp, i64, ip, ctypes.POINTER(f32), ctypes.POINTER(f32),
+                                   ctypes.c_uint64, ctypes.c_uint64, ip, i32, i32, f32, vp, vp, vp, vp, vp, i32, op,
+                                   vp, i32, vp, ctypes.c_size_t, vp, ctypes.c_size_t, vp, ctypes.POINTER(f32)]
+    for name in ('pinn_optim_step', 'pinn_optim_step_at', 'pinn_residual_optim_step', 'pinn_fit_steps'):
         getattr(lib, name).restype = i32
     lib.pinn_set_tanh_mode.argtypes = [vp, i32]
     lib.pinn_set_tanh_mode.restype = i32
@@ -178,10 +163,9 @@ def bind(lib):
     lib.pinn_last_wgrad_ms.restype = f32
     lib.pinn_last_kernel_name.restype = ctypes.c_char_p
     lib.pinn_last_wgrad_kernel_name.restype = ctypes.c_char_p
-    if hasattr(lib, 'pinn_reduce_rows'):                         # (an experiment build of an earlier source tree may lack them)
-        lib.pinn_reduce_rows.argtypes = [vp, i32, i32, vp, i32, vp, vp, vp, vp, vp, i32, op, vp, i32, vp]
-        lib.pinn_reduce_rows.restype = i32
-        lib.pinn_last_reduce_kernel_name.restype = ctypes.c_char_p
+    lib.pinn_reduce_rows.argtypes = [vp, i32, i32, vp, i32, vp, vp, vp, vp, vp, i32, op, vp, i32, vp]
+    lib.pinn_reduce_rows.restype = i32
+    lib.pinn_last_reduce_kernel_name.restype = ctypes.c_char_p
     if hasattr(lib, 'pinn_debug_phase_buffer'):                  # -DPINN_DEBUG_ABI experiment builds only
         lib.pinn_debug_phase_buffer.argtypes = [vp]
     lib.pinn_debug_wgx_chunk_bytes.argtypes = [vp, ctypes.c_longlong]
@@ -220,17 +204,16 @@ def bind(lib):
     lib.pinn_resample_redraw.argtypes = [vp, i64, i32, i64, u64, u64, vp, vp, vp, ctypes.c_size_t, vp]
     lib.pinn_resample_redraw.restype = i32
     for name in ('pinn_create', 'pinn_create_ex', 'pinn_destroy', 'pinn_layout', 'pinn_jet_forward', 'pinn_jet_forward_ws', 'pinn_jet_backward',
-                 'pinn_residual_step', 'pinn_residual_adam_step', 'pinn_adam_step', 'pinn_adam_step_at'):
+                 'pinn_residual_step'):
         getattr(lib, name).restype = i32
     return lib
 
 
 ABI_SYMBOLS = ('pinn_create', 'pinn_create_ex', 'pinn_destroy', 'pinn_layout', 'pinn_workspace_bytes', 'pinn_jet_forward', 'pinn_jet_forward_ws',
-               'pinn_jet_backward', 'pinn_residual_step', 'pinn_residual_step_add', 'pinn_residual_adam_step', 'pinn_adam_step', 'pinn_adam_step_at', 'pinn_sample_points', 'pinn_fit_steps', 'pinn_fit_steps_graph', 'pinn_fit_ctrl_bytes', 'pinn_set_gemm_mode', 'pinn_set_tanh_mode', 'pinn_profile_tile',
+               'pinn_jet_backward', 'pinn_residual_step', 'pinn_residual_step_add', 'pinn_sample_points', 'pinn_fit_steps', 'pinn_fit_ctrl_bytes', 'pinn_set_gemm_mode', 'pinn_set_tanh_mode', 'pinn_profile_tile',
                'pinn_last_tile_ms', 'pinn_last_wgrad_ms', 'pinn_last_kernel_name', 'pinn_last_wgrad_kernel_name', 'pinn_debug_last_kernel',
                'pinn_debug_prepass_in_kernel', 'pinn_debug_wgx_chunk_bytes', 'pinn_debug_max_wgs_per_cu', 'pinn_debug_fit_persistent', 'pinn_fit_chunk_status', 'pinn_set_act_params', 'pinn_debug_fit_onecu_rounds', 'pinn_debug_fit_graph_stats', 'pinn_last_launch_info',
-               'pinn_optim_step', 'pinn_optim_step_at', 'pinn_residual_optim_step', 'pinn_fit_steps_optim', 'pinn_fit_steps_optim_graph',
-               'pinn_fit_steps_optim_sched', 'pinn_reduce_rows', 'pinn_last_reduce_kernel_name', 'pinn_port_probe',
+               'pinn_optim_step', 'pinn_optim_step_at', 'pinn_residual_optim_step', 'pinn_reduce_rows', 'pinn_last_reduce_kernel_name', 'pinn_port_probe',
                'pinn_lbfgs_ctrl_bytes', 'pinn_lbfgs_workspace_bytes', 'pinn_lbfgs_direction',
                'pinn_balance_state_bytes', 'pinn_balance_workspace_bytes', 'pinn_balance_init', 'pinn_balance_terms',
                'pinn_resample_workspace_bytes', 'pinn_resample_points', 'pinn_resample_redraw',
@@ -286,17 +269,6 @@ def _check(t, name, dtype=torch.float32):
         return
     if t.dtype != dtype or not t.is_contiguous():
         raise ValueError(f'{name} must be a contiguous {dtype} tensor')
-
-
-def _rule(lr, betas, eps, optim):
-    """ the update-rule arguments of an entry point: plain Adam's four numbers, or the `Optim` of the pinn_optim_t family """
-    return (float(lr), float(betas[0]), float(betas[1]), float(eps)) if optim is None else (ctypes.byref(optim), )
-
-
-# Net.fit_steps: (has lr_steps, has optim, has ctrl) -> exported symbol (a schedule always carries an Optim: plain Adam becomes OPT_ADAM)
-_FIT_STEPS = {(False, False, False): 'pinn_fit_steps', (False, False, True): 'pinn_fit_steps_graph',
-              (False, True, False): 'pinn_fit_steps_optim', (False, True, True): 'pinn_fit_steps_optim_graph',
-              (True, True, False): 'pinn_fit_steps_optim_sched', (True, True, True): 'pinn_fit_steps_optim_sched'}
 
 
 class Net:
@@ -476,33 +448,31 @@ class Net:
                                                     _ptr(workspace), workspace.numel() * workspace.element_size(),
                                                     _stream(xs) if stream is None else stream))
 
-    def residual_adam_step(self, residual, params, xs, grads, workspace, exp_avg, exp_avg_sq, mask, step_tensor, step,
-                           lr, betas=(0.9, 0.999), eps=1e-8, dir_cols=(), n2=0, ic_streams=None, ic_const=0.0,
-                           loss_out=None, stream=None, optim=None):
-        """ `loss_out`: device ADDRESS (int) that also receives the loss of the step; `stream`: handle from `stream_of`
-        when the caller has looked it up already (a fit loop asks once, not per iteration); `optim`: an `Optim` -- the update
-        rule of pinn_residual_optim_step instead of plain Adam's (lr, betas, eps) """
+    def residual_optim_step(self, residual, params, xs, grads, workspace, exp_avg, exp_avg_sq, mask, step_tensor, step, optim,
+                            dir_cols=(), n2=0, ic_streams=None, ic_const=0.0, loss_out=None, stream=None):
+        """ one fused iteration with the update rule of `optim` (an `Optim`; include/pinn.h pinn_residual_optim_step). `loss_out`: device
+        ADDRESS (int) that also receives the loss of the step; `stream`: handle from `stream_of` when the caller has looked it up already
+        (a fit loop asks once, not per iteration) """
         for t, name in ((params, 'params'), (xs, 'xs'), (grads, 'grads'), (ic_streams, 'ic_streams'),
                         (exp_avg, 'exp_avg'), (exp_avg_sq, 'exp_avg_sq')):
             _check(t, name)
         _check(mask, 'mask', torch.uint8)
         _check(step_tensor, 'step', torch.int32)
         dirs, nd = self._dirs(dir_cols)
-        fn = self.lib.pinn_residual_adam_step if optim is None else self.lib.pinn_residual_optim_step
         with _on_device(params):
-            self._raise(fn(
+            self._raise(self.lib.pinn_residual_optim_step(
                 self.handle, ctypes.byref(residual), _ptr(params), _ptr(xs), xs.shape[0], dirs, nd, n2, _ptr(ic_streams),
                 float(ic_const), _ptr(grads), _ptr(exp_avg), _ptr(exp_avg_sq), _ptr(mask), _ptr(step_tensor), int(step),
-                *_rule(lr, betas, eps, optim), None if loss_out is None else ctypes.c_void_p(loss_out), _ptr(workspace),
+                ctypes.byref(optim), None if loss_out is None else ctypes.c_void_p(loss_out), _ptr(workspace),
                 workspace.numel() * workspace.element_size(), _stream(xs) if stream is None else stream))
 
     def fit_steps(self, residual, params, xs, columns, seed, call_index0, grads, workspace, exp_avg, exp_avg_sq, mask,
-                  step_tensor, step0, lr, betas, eps, loss_history, k_steps, dir_cols=(), n2=0, ic_const=0.0, stream=None, ctrl=None,
-                  optim=None, lr_steps=None):
-        """ `k_steps` iterations of the fit loop (sample -> fused step -> Adam) enqueued by one call (include/pinn.h
-        pinn_fit_steps); `xs` is the [N, d] batch buffer every iteration overwrites, `loss_history` a float32 device tensor
-        with at least k_steps entries. `lr_steps`: the learning rate of each of the k_steps iterations (a schedule; include/pinn.h
-        pinn_fit_steps_optim_sched) -- with or without `ctrl`, with `optim` or plain Adam's (betas, eps); `lr` is then not used. """
+                  step_tensor, step0, optim, loss_history, k_steps, dir_cols=(), n2=0, ic_const=0.0, stream=None, ctrl=None, lr_steps=None):
+        """ `k_steps` iterations of the fit loop (sample -> fused step -> update by the rule of `optim`) enqueued by one call
+        (include/pinn.h pinn_fit_steps); `xs` is the [N, d] batch buffer every iteration overwrites, `loss_history` a float32 device
+        tensor with at least k_steps entries. `ctrl`: a uint8 device tensor of pinn_fit_ctrl_bytes() bytes -- the chunk as one launch or
+        one replayable launch graph where the library finds that it applies; None: the eager loop. `lr_steps`: the learning rate of each
+        of the k_steps iterations (a schedule); None: the constant rate of `optim`. """
         for t, name in ((params, 'params'), (xs, 'xs'), (grads, 'grads'), (exp_avg, 'exp_avg'), (exp_avg_sq, 'exp_avg_sq'),
                         (loss_history, 'loss_history')):
             _check(t, name)
@@ -515,27 +485,19 @@ class Net:
         a = (ctypes.c_float * d)(*[float(c[1]) for c in columns])
         b = (ctypes.c_float * d)(*[float(c[2]) for c in columns])
         dirs, nd = self._dirs(dir_cols)
-        # (`optim`: the update rule of pinn_fit_steps_optim / _optim_graph instead of plain Adam's lr, betas, eps)
         rates = None
         if lr_steps is not None:
             if len(lr_steps) != k_steps:
                 raise ValueError(f'lr_steps must hold {k_steps} rates, one per iteration')
             rates = (ctypes.c_float * max(1, k_steps))(*[float(v) for v in lr_steps])
-            if optim is None:       # (plain Adam as a rule of the family: the same arithmetic, include/pinn.h pinn_optim_t)
-                optim = Optim.build(OPT_ADAM, lr, betas=betas, eps=eps)
-        args = (self.handle, ctypes.byref(residual), _ptr(params), _ptr(xs), xs.shape[0], kind, a, b,
-                int(seed) & (2 ** 64 - 1), int(call_index0), dirs, nd, n2, float(ic_const), _ptr(grads), _ptr(exp_avg),
-                _ptr(exp_avg_sq), _ptr(mask), _ptr(step_tensor), int(step0), *_rule(lr, betas, eps, optim),
-                _ptr(loss_history), int(k_steps), _ptr(workspace), workspace.numel() * workspace.element_size())
-        # `ctrl`: a uint8 device tensor of pinn_fit_ctrl_bytes() bytes -- the chunk as one replayable launch graph (the library falls
-        # back to the eager loop by itself where a graph does not apply); the schedule's entry point takes one always, NULL included
-        if ctrl is not None or rates is not None:
-            args += (_ptr(ctrl), 0 if ctrl is None else ctrl.numel() * ctrl.element_size())
-        args += (_stream(xs) if stream is None else stream, )
-        if rates is not None:
-            args += (rates, )
         with _on_device(params):
-            self._raise(getattr(self.lib, _FIT_STEPS[rates is not None, optim is not None, ctrl is not None])(*args))
+            self._raise(self.lib.pinn_fit_steps(
+                self.handle, ctypes.byref(residual), _ptr(params), _ptr(xs), xs.shape[0], kind, a, b,
+                int(seed) & (2 ** 64 - 1), int(call_index0), dirs, nd, n2, float(ic_const), _ptr(grads), _ptr(exp_avg),
+                _ptr(exp_avg_sq), _ptr(mask), _ptr(step_tensor), int(step0), ctypes.byref(optim),
+                _ptr(loss_history), int(k_steps), _ptr(workspace), workspace.numel() * workspace.element_size(),
+                _ptr(ctrl), 0 if ctrl is None else ctrl.numel() * ctrl.element_size(),
+                _stream(xs) if stream is None else stream, rates))
 
     def sample_points(self, xs, columns, seed, call_index, stream=None):
         """ fill xs [N, d] on the device: columns = [(kind, a, b), ...] with kind SAMPLE_UNIFORM (a + (b - a) u),
@@ -552,7 +514,10 @@ class Net:
                                                     int(call_index), _stream(xs) if stream is None else stream))
         return xs
 
-    def _update_step(self, name, rule, params, grads, exp_avg, exp_avg_sq, mask, step, at, loss_out, stream):
+    def optim_step(self, params, grads, exp_avg, exp_avg_sq, mask, step, optim, at=0, loss_out=None, stream=None):
+        """ one update by the rule of `optim` (an `Optim`; include/pinn.h pinn_optim_step / pinn_optim_step_at). `step`: int32 device
+        counter; at > 0: the host's 1-based step count (one launch, counter mirrored); loss_out: device ADDRESS (int) that receives
+        grads[off_loss] in the same launch (at > 0 only) """
         for t, what in ((params, 'params'), (grads, 'grads'), (exp_avg, 'exp_avg'), (exp_avg_sq, 'exp_avg_sq')):
             _check(t, what)
         _check(mask, 'mask', torch.uint8)
@@ -560,20 +525,14 @@ class Net:
         head = (_ptr(params), _ptr(grads), _ptr(exp_avg), _ptr(exp_avg_sq), _ptr(mask), params.numel(), _ptr(step))
         with _on_device(params):
             if at > 0:
-                self._raise(getattr(self.lib, name + '_at')(*head, int(at), *rule, None if loss_out is None else ctypes.c_void_p(loss_out),
-                                                            int(self.layout.off_loss), _stream(params) if stream is None else stream))
+                self._raise(self.lib.pinn_optim_step_at(*head, int(at), ctypes.byref(optim), None if loss_out is None else ctypes.c_void_p(loss_out),
+                                                        int(self.layout.off_loss), _stream(params) if stream is None else stream))
             else:
-                self._raise(getattr(self.lib, name)(*head, *rule, _stream(params)))
+                self._raise(self.lib.pinn_optim_step(*head, ctypes.byref(optim), _stream(params)))
 
-    def adam_step(self, params, grads, exp_avg, exp_avg_sq, mask, step, lr, betas=(0.9, 0.999), eps=1e-8, at=0,
-                  loss_out=None, stream=None):
-        """ `step`: int32 device counter; at > 0: the host's 1-based step count (one launch, counter mirrored);
-        loss_out: device ADDRESS (int) that receives grads[off_loss] in the same launch (at > 0 only) """
-        self._update_step('pinn_adam_step', _rule(lr, betas, eps, None), params, grads, exp_avg, exp_avg_sq, mask, step, at, loss_out, stream)
-
-    def optim_step(self, params, grads, exp_avg, exp_avg_sq, mask, step, optim, at=0, loss_out=None, stream=None):
-        """ `adam_step` with the update rule of `optim` (an `Optim`; include/pinn.h pinn_optim_step / pinn_optim_step_at) """
-        self._update_step('pinn_optim_step', _rule(None, None, None, optim), params, grads, exp_avg, exp_avg_sq, mask, step, at, loss_out, stream)
+    def adam_step(self, params, grads, exp_avg, exp_avg_sq, mask, step, lr, betas=(0.9, 0.999), eps=1e-8, **kwargs):
+        """ `optim_step` with plain Adam's numbers """
+        self.optim_step(params, grads, exp_avg, exp_avg_sq, mask, step, Optim.build(OPT_ADAM, lr, betas=betas, eps=eps), **kwargs)
 
     # ---- L-BFGS (include/pinn.h pinn_lbfgs_direction) --------------------------------------------------------------------------------
     def lbfgs_ctrl_doubles(self, history):

@@ -3,7 +3,7 @@ per-iteration arithmetic runs in the HIP kernels behind include/pinn.h.
 
 Two step paths share every kernel:
   * fused   -- the equation was lowered to a residual program (trace.py): ONE call of pinn_residual_step does
-               forward jets, ansatz, residual, MSE and the whole reverse sweep; then pinn_adam_step. No torch
+               forward jets, ansatz, residual, MSE and the whole reverse sweep; then pinn_optim_step_at. No torch
                arithmetic and no host synchronisation inside the loop (losses stay on the device).
   * generic -- anything else the reference API allows (trainable `V` variables, callable ICs holding variables,
                constraint terms, user criteria): pinn_jet_forward hands the derivative streams to the user's own
@@ -66,7 +66,7 @@ class FlatOptimizer:
             raise NotImplementedError(f'the HIP optimizer kernels do not carry torch.optim.{name}(lr={lr}, **{kwargs})')
         self.name, self.hyper_parameters = name, hyper
         self.torch_kwargs = dict(kwargs)            # (what `TorchOptimizerAdapter.continuing` hands torch.optim)
-        self.optim = engine.Optim.build(self.RULES[name][0], **hyper)       # None: plain Adam through the Adam entry points (FlatAdam)
+        self.optim = engine.Optim.build(self.RULES[name][0], **hyper)       # (None: FlatLBFGS, which has entry points of its own)
         self.model, self.lr = model, hyper['lr']
         self.betas, self.eps = tuple(hyper.get('betas', (0.0, 0.0))), hyper.get('eps', 0.0)
         self._take_state(model)
@@ -91,7 +91,7 @@ class FlatOptimizer:
     def _take_state(self, model):
         # the moment buffers and the device step counter belong to the MODEL and are zeroed here: every fit call builds a fresh
         # optimizer (reference :419-422) -- at the same device addresses, so that the launch graph a previous fit call recorded
-        # (pinn_fit_steps_graph keys on the addresses its nodes carry) is replayed instead of re-recorded. One live
+        # (pinn_fit_steps keys on the addresses its nodes carry) is replayed instead of re-recorded. One live
         # optimizer per model: the Solver never keeps an old one.
         state = getattr(model, '_adam_state', None)
         if state is None or state[0].shape != model.flat.shape or state[0].device != model.flat.device:
@@ -149,7 +149,7 @@ class FlatOptimizer:
 
     def set_lr(self, lr):
         """ the learning rate of the coming step(s) (a schedule, Solver.fit(lr_scheduler=...)): every eager call hands it to the library by
-        value, through `lr` (plain Adam, L-BFGS) or the `Optim` struct """
+        value, through the `Optim` struct (L-BFGS: through `lr`) """
         self.lr = float(lr)
         if self.optim is not None:
             self.optim.lr = self.lr
@@ -174,21 +174,12 @@ class FlatOptimizer:
 
 
 class FlatAdam(FlatOptimizer):
-    """ plain torch.optim.Adam (lr, betas, eps): the default of `Solver.fit`, through the Adam entry points of the library """
+    """ plain torch.optim.Adam (lr, betas, eps): the default of `Solver.fit` -- the rule 'Adam' without weight decay """
     def __init__(self, model, lr=0.005, betas=(0.9, 0.999), eps=1e-8, weight_decay=0, amsgrad=False, **kwargs):
         if weight_decay != 0 or amsgrad or kwargs:
             raise NotImplementedError('FlatAdam is plain Adam (lr, betas, eps); got '
                                       f'weight_decay={weight_decay}, amsgrad={amsgrad}, {kwargs}')
-        self.name, self.optim = 'Adam', None
-        self.hyper_parameters = dict(lr=lr, betas=betas, eps=eps, weight_decay=0)
-        self.torch_kwargs = dict(betas=betas, eps=eps)
-        self.model, self.lr, self.betas, self.eps = model, lr, betas, eps
-        self._take_state(model)
-
-    def step(self, grads, loss_out=None, stream=None):
-        self.t += 1
-        self.model.net.adam_step(self.model.flat, grads, self.exp_avg, self.exp_avg_sq, self.mask, self.step_count,
-                                 self.lr, self.betas, self.eps, at=self.t, loss_out=loss_out, stream=stream)
+        super().__init__(model, 'Adam', lr=lr, betas=betas, eps=eps)
 
 
 class FlatLBFGS(FlatOptimizer):
@@ -1438,7 +1429,7 @@ class Solver:
         """ `fit(lr_scheduler=spec, lr_scheduler_kwargs=kwargs)`. Semantics: torch's `opt.step(); sched.step()` per iteration; the rate of
         iteration k is what `param_groups[0]['lr']` reads in front of step k. The rates are torch's own: its scheduler code runs on the host,
         over the real optimizer on the torch path, over a one-parameter shadow optimizer for the flat optimizers -- there they are drawn a chunk
-        ahead into a queue and travel to the kernels per iteration (include/pinn.h pinn_fit_steps_optim_sched). fresh: a new optimizer. """
+        ahead into a queue and travel to the kernels per iteration (include/pinn.h pinn_fit_steps, lr_steps). fresh: a new optimizer. """
         if spec is None:
             if fresh:
                 self.lr_scheduler, self._lr_queue = None, []
@@ -1720,7 +1711,7 @@ class Solver:
             self._rate_end(rate)
 
     FIT_CHUNK = 128             # iterations per pinn_fit_steps call (progress bar / KeyboardInterrupt granularity)
-    FIT_CTRL_ON_HOST = False    # (tests on the CPU emulator: the control block of pinn_fit_steps_graph in host memory)
+    FIT_CTRL_ON_HOST = False    # (tests on the CPU emulator: the control block of pinn_fit_steps in host memory)
     GRAPH_MAX_BATCH = 4096      # batches up to this size replay their chunks as one launch graph (+16 % at batch 100, +1 % at 4 096)
 
     def _device_columns(self, sampler):
@@ -1750,7 +1741,7 @@ class Solver:
         own = sampler.device_key() if (sampler is not None and hasattr(sampler, 'device_key')) else None
         rank, _ = self._world()
         # small batches (the latency regime): each chunk as ONE replayable launch graph; the control block the kernels read their
-        # per-iteration values from belongs to the solver (include/pinn.h pinn_fit_steps_graph)
+        # per-iteration values from belongs to the solver (include/pinn.h pinn_fit_steps, ctrl)
         ctrl = None
         if batch <= self.GRAPH_MAX_BATCH and (xs.is_cuda or self.FIT_CTRL_ON_HOST) and os.environ.get('PYDENS_AMD_FIT_GRAPH', '1') != '0':
             if getattr(self, '_fit_ctrl', None) is None or self._fit_ctrl.device != xs.device:
@@ -1770,9 +1761,9 @@ class Solver:
                 rates = self._draw_rates(k) if self.lr_scheduler is not None else None
                 try:
                     model.net.fit_steps(self.program, model.flat, xs, columns, seed, call0, self.grads, ws, adam.exp_avg,
-                                        adam.exp_avg_sq, adam.mask, adam.step_count, adam.t + 1, adam.lr, adam.betas, adam.eps,
+                                        adam.exp_avg_sq, adam.mask, adam.step_count, adam.t + 1, adam.optim,
                                         history[it:it + k], k, dir_cols=spec.dir_cols, n2=n2, ic_const=model.kernel_ic_const(),
-                                        stream=stream, ctrl=ctrl, optim=adam.optim, lr_steps=rates)
+                                        stream=stream, ctrl=ctrl, lr_steps=rates)
                     if os.environ.get('PYDENS_AMD_FIT_PERSIST') == '1' and model.net.lib.pinn_fit_chunk_status() != 0:
                         # the opt-in GRID form of the one-launch chunk gave up at its device-wide wait: nothing of the chunk was applied
                         # (include/pinn.h pinn_fit_chunk_status; the check synchronises with the device once per chunk)
@@ -1809,10 +1800,9 @@ class Solver:
         ws = model.workspace(xs.shape[0], spec.nd, spec.n2p)
         if adam is not None:
             adam.t += 1
-            model.net.residual_adam_step(self.program, model.flat, xs, self.grads, ws, adam.exp_avg, adam.exp_avg_sq,
-                                         adam.mask, adam.step_count, adam.t, adam.lr, adam.betas, adam.eps,
-                                         dir_cols=spec.dir_cols, n2=n2, ic_streams=ic_streams,
-                                         ic_const=model.kernel_ic_const(), loss_out=loss_out, stream=stream, optim=adam.optim)
+            model.net.residual_optim_step(self.program, model.flat, xs, self.grads, ws, adam.exp_avg, adam.exp_avg_sq,
+                                          adam.mask, adam.step_count, adam.t, adam.optim, dir_cols=spec.dir_cols, n2=n2,
+                                          ic_streams=ic_streams, ic_const=model.kernel_ic_const(), loss_out=loss_out, stream=stream)
             return
         # data parallel: this rank's share of a GLOBAL batch (shares may differ by one point: the true global count divides)
         n_global = self._global_batch if (world > 1 and getattr(self, '_global_batch', None)) else xs.shape[0] * world

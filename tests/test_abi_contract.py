@@ -175,7 +175,9 @@ def test_sampler_and_adam_argument_checks(lib):
     assert lib.pinn_sample_points(_ptr(xs), 8, 3, bad_kind, a, b, 1, 0, None) != 0 and 'kind' in _err(lib)
     p, g, m, v = (torch.zeros(16) for _ in range(4))
     step = torch.zeros(1, dtype=torch.int32)
-    assert lib.pinn_adam_step(_ptr(p), None, _ptr(m), _ptr(v), None, 16, _ptr(step), 0.1, 0.9, 0.999, 1e-8, None) != 0
-    assert lib.pinn_adam_step_at(_ptr(p), _ptr(g), _ptr(m), _ptr(v), None, 16, _ptr(step), 0, 0.1, 0.9, 0.999, 1e-8, None, 0, None) != 0
-    assert lib.pinn_adam_step(_ptr(p), _ptr(g), _ptr(m), _ptr(v), None, 0, _ptr(step), 0.1, 0.9, 0.999, 1e-8, None) == 0
+    from pydens_amd import engine
+    adam = ctypes.byref(engine.Optim.build(engine.OPT_ADAM, 0.1, betas=(0.9, 0.999), eps=1e-8))
+    assert lib.pinn_optim_step(_ptr(p), None, _ptr(m), _ptr(v), None, 16, _ptr(step), adam, None) != 0 and 'null' in _err(lib)
+    assert lib.pinn_optim_step_at(_ptr(p), _ptr(g), _ptr(m), _ptr(v), None, 16, _ptr(step), 0, adam, None, 0, None) != 0 and 'step' in _err(lib)
+    assert lib.pinn_optim_step(_ptr(p), _ptr(g), _ptr(m), _ptr(v), None, 0, _ptr(step), adam, None) == 0
     assert np.all(p.numpy() == 0)

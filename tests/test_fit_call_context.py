@@ -1,6 +1,7 @@
 """ The context of a fit chunk belongs to the call that carries it (pinn_abi.cpp: StepCall / FitCall / StepTail handed down by reference, no
 state of the calling thread): a chunk that fails leaves nothing behind for the next, unrelated step call; two nets driven alternately on one
-thread follow the trajectories they follow alone; and `engine.Net.fit_steps` reaches the exported symbol its arguments name. CPU only, on the
+thread follow the trajectories they follow alone; `engine.Net.fit_steps` reaches pinn_fit_steps with the header's arguments, and that one
+entry point runs the same chunk with or without a control block and a rate table. CPU only, on the
 emulator build of the product's own pinn_abi.cpp; every comparison is of bits. """
 import ctypes
 import os
@@ -63,16 +64,15 @@ class Run:
     def chunk(self, k):
         """ k iterations as ONE call with a control block (width 16, a batch of four tiles: the one-CU chunk kernel) """
         self.net.fit_steps(self.residual, self.params, self.xs, COLUMNS, SEED, self.at, self.grads, self.ws, self.m, self.v, self.mask, self.step,
-                           self.at + 1, LR, (0.9, 0.999), 1e-8, self.losses[self.at:self.at + k], k, dir_cols=(0, 1), n2=N2, ctrl=self.ctrl,
-                           optim=self.optim)
+                           self.at + 1, self.optim, self.losses[self.at:self.at + k], k, dir_cols=(0, 1), n2=N2, ctrl=self.ctrl)
         self.at += k
 
     def steps(self, k):
         """ k iterations, each a sampler call and a pinn_residual_optim_step """
         for _ in range(k):
             self.net.sample_points(self.xs, COLUMNS, SEED, self.at)
-            self.net.residual_adam_step(self.residual, self.params, self.xs, self.grads, self.ws, self.m, self.v, self.mask, self.step,
-                                        self.at + 1, LR, dir_cols=(0, 1), n2=N2, loss_out=self.losses.data_ptr() + 4 * self.at, optim=self.optim)
+            self.net.residual_optim_step(self.residual, self.params, self.xs, self.grads, self.ws, self.m, self.v, self.mask, self.step,
+                                         self.at + 1, self.optim, dir_cols=(0, 1), n2=N2, loss_out=self.losses.data_ptr() + 4 * self.at)
             self.at += 1
 
     def state(self):
@@ -92,9 +92,9 @@ def test_a_failed_chunk_leaves_nothing_behind(lib):
 
     def adam_step(run):
         run.xs.copy_(batch)
-        rc = lib.pinn_residual_adam_step(run.net.handle, ctypes.byref(run.residual), _ptr(run.params), _ptr(run.xs), BATCH, dirs, ND, N2, None, 0.0,
-                                         _ptr(run.grads), _ptr(run.m), _ptr(run.v), _ptr(run.mask), _ptr(run.step), 1, LR, 0.9, 0.999, 1e-8,
-                                         _ptr(run.losses), _ptr(run.ws), run.ws_bytes, None)
+        rc = lib.pinn_residual_optim_step(run.net.handle, ctypes.byref(run.residual), _ptr(run.params), _ptr(run.xs), BATCH, dirs, ND, N2, None, 0.0,
+                                          _ptr(run.grads), _ptr(run.m), _ptr(run.v), _ptr(run.mask), _ptr(run.step), 1, ctypes.byref(run.optim),
+                                          _ptr(run.losses), _ptr(run.ws), run.ws_bytes, None)
         assert rc == 0, lib.pinn_last_error().decode()
         return run.state()
 
@@ -106,10 +106,10 @@ def test_a_failed_chunk_leaves_nothing_behind(lib):
 
     def chunk(workspace_bytes):
         """ three iterations with a control block and a schedule: the one-launch request travels with this call """
-        return lib.pinn_fit_steps_optim_sched(run.net.handle, ctypes.byref(run.residual), _ptr(run.params), _ptr(run.xs), BATCH, kind, lo, hi, SEED, 0,
-                                              dirs, ND, N2, 0.0, _ptr(run.grads), _ptr(run.m), _ptr(run.v), _ptr(run.mask), _ptr(run.step), 1,
-                                              ctypes.byref(run.optim), _ptr(run.losses), 3, _ptr(run.ws), workspace_bytes, _ptr(run.ctrl),
-                                              run.ctrl.numel(), None, rates)
+        return lib.pinn_fit_steps(run.net.handle, ctypes.byref(run.residual), _ptr(run.params), _ptr(run.xs), BATCH, kind, lo, hi, SEED, 0,
+                                  dirs, ND, N2, 0.0, _ptr(run.grads), _ptr(run.m), _ptr(run.v), _ptr(run.mask), _ptr(run.step), 1,
+                                  ctypes.byref(run.optim), _ptr(run.losses), 3, _ptr(run.ws), workspace_bytes, _ptr(run.ctrl),
+                                  run.ctrl.numel(), None, rates)
     # pinn_workspace_bytes is an upper bound over every form a step may take (one byte less than IT still runs the chunk), so the
     # byte that matters is read from the library: a chunk one byte short of what its step needs, and one with no room at all
     assert chunk(1) != 0
@@ -158,28 +158,89 @@ class RecordingLib:
 @pytest.mark.parametrize('with_ctrl', [False, True])
 @pytest.mark.parametrize('with_rates', [False, True])
 def test_fit_steps_reaches_the_symbol_its_arguments_name(with_optim, with_ctrl, with_rates):
+    """ one chunk entry point whatever the arguments: pinn_fit_steps with the 29 arguments of include/pinn.h """
     from pydens_amd import engine
     rec = RecordingLib()
     net = engine.Net.__new__(engine.Net)
     net.lib, net.handle = rec, None
     n = 32
     f32 = lambda *shape: torch.zeros(*shape)
-    optim = engine.Optim.build(engine.OPT_SGD, 0.5, momentum=0.9) if with_optim else None
+    optim = engine.Optim.build(engine.OPT_SGD, 0.5, momentum=0.9) if with_optim else engine.Optim.build(engine.OPT_ADAM, LR, betas=(0.9, 0.999), eps=1e-8)
     ctrl = torch.zeros(64, dtype=torch.uint8) if with_ctrl else None
     net.fit_steps(engine.Residual(), f32(n), f32(8, 2), COLUMNS, SEED, 0, f32(n), f32(16), f32(n), f32(n), torch.ones(n, dtype=torch.uint8),
-                  torch.zeros(1, dtype=torch.int32), 1, LR, (0.9, 0.999), 1e-8, f32(3), 3, dir_cols=(0, 1), n2=N2, ctrl=ctrl, optim=optim,
+                  torch.zeros(1, dtype=torch.int32), 1, optim, f32(3), 3, dir_cols=(0, 1), n2=N2, ctrl=ctrl,
                   lr_steps=[LR, LR / 2, LR / 4] if with_rates else None)
     (name, argc, args), = [c for c in rec.calls if c[0] != 'pinn_destroy']
-    # (include/pinn.h: 29 arguments with Adam's four numbers, 26 with a pinn_optim_t; a control block adds two, a schedule its table)
-    want = {(False, False, False): ('pinn_fit_steps', 29), (False, False, True): ('pinn_fit_steps_graph', 31),
-            (False, True, False): ('pinn_fit_steps_optim', 26), (False, True, True): ('pinn_fit_steps_optim_graph', 28),
-            (True, False, False): ('pinn_fit_steps_optim_sched', 29), (True, False, True): ('pinn_fit_steps_optim_sched', 29),
-            (True, True, False): ('pinn_fit_steps_optim_sched', 29), (True, True, True): ('pinn_fit_steps_optim_sched', 29)}
-    assert (name, argc) == want[with_rates, with_optim, with_ctrl]
-    if with_rates:
-        # a schedule always goes through the family's entry point: plain Adam as an OPT_ADAM struct with the caller's numbers
-        rule = args[20]._obj                # (what ctypes.byref wraps)
-        assert rule.rule == (engine.OPT_SGD if with_optim else engine.OPT_ADAM)
-        assert with_optim or (rule.lr, rule.beta1, rule.beta2) == (ctypes.c_float(LR).value, ctypes.c_float(0.9).value, ctypes.c_float(0.999).value)
+    assert (name, argc) == ('pinn_fit_steps', 29)
+    rule = args[20]._obj                # (what ctypes.byref wraps: the caller's struct itself, field for field)
+    assert rule is optim
+    if with_optim:
+        assert (rule.rule, rule.lr, rule.momentum) == (engine.OPT_SGD, 0.5, ctypes.c_float(0.9).value)
+    else:
+        assert (rule.rule, rule.lr, rule.beta1, rule.beta2, rule.eps) == \
+            (engine.OPT_ADAM, ) + tuple(ctypes.c_float(v).value for v in (LR, 0.9, 0.999, 1e-8))
+    assert (args[25] is None, args[26]) == (not with_ctrl, 64 if with_ctrl else 0)         # ctrl is (None, 0) when absent
+    if with_rates:                      # the rates array sits in the last position
         assert [args[28][i] for i in range(3)] == [ctypes.c_float(v).value for v in (LR, LR / 2, LR / 4)]
-        assert (args[25] is None, args[26]) == (not with_ctrl, 64 if with_ctrl else 0)
+    else:
+        assert args[28] is None
+
+
+def _one_chunk(lib, optim, form):
+    """ four iterations on a fresh Run (launch graphs / eager loop: pinn_debug_fit_persistent 0): 'steps' -- four sample_points +
+    residual_optim_step calls; otherwise ONE pinn_fit_steps call, with a control block and / or a constant rate table as `form` names """
+    run = Run(lib, 0)
+    run.optim = optim
+    if form == 'steps':
+        run.steps(4)
+    else:
+        run.net.fit_steps(run.residual, run.params, run.xs, COLUMNS, SEED, 0, run.grads, run.ws, run.m, run.v, run.mask, run.step, 1, optim,
+                          run.losses[:4], 4, dir_cols=(0, 1), n2=N2, ctrl=run.ctrl if 'ctrl' in form else None,
+                          lr_steps=[optim.lr] * 4 if 'rates' in form else None)
+    return run.state()
+
+
+@pytest.mark.parametrize('rule', ['adam', 'sgd'])
+def test_one_entry_point_runs_the_same_chunk_in_every_form(lib, rule):
+    """ what the dispatch table used to imply: without `ctrl`, with `ctrl`, with a constant `lr_steps` and with both, the chunk is the same
+    four iterations -- parameters, both state arrays, gradients, losses, step counter and the batch left in xs, bit for bit -- and those
+    are four sample_points + residual_optim_step calls """
+    from pydens_amd import engine
+    build = {'adam': lambda: engine.Optim.build(engine.OPT_ADAM, LR, betas=(0.9, 0.999), eps=1e-8),
+             'sgd': lambda: engine.Optim.build(engine.OPT_SGD, LR, momentum=0.9)}[rule]
+    want = _one_chunk(lib, build(), 'steps')
+    assert int(want['step']) == 4 and float(want['losses'][3]) > 0.0 and bool((want['m'] != 0).any())
+    for form in ('plain', 'ctrl', 'rates', 'ctrl+rates'):
+        _same(_one_chunk(lib, build(), form), want, form)
+
+
+@pytest.mark.parametrize('bad', [dict(betas=(0.9, 1.0)), dict(eps=-1.0)], ids=['beta2_is_1', 'negative_eps'])
+def test_adam_numbers_the_library_refuses(lib, bad):
+    """ plain Adam's numbers pass through the checks of the family: beta2 = 1 and eps < 0 are refused by every entry point that updates,
+    with a message, and nothing is launched -- every buffer, the batch in xs among them, stays as it was """
+    from pydens_amd import engine
+    optim = engine.Optim.build(engine.OPT_ADAM, LR, **dict(dict(betas=(0.9, 0.999), eps=1e-8), **bad))
+    run = Run(lib, 2)
+    run.xs.copy_(torch.rand(BATCH, 2, generator=torch.Generator().manual_seed(9)))
+    run.grads.normal_(generator=torch.Generator().manual_seed(10))
+    before = run.state()
+    dirs = (ctypes.c_int * 2)(0, 1)
+    kind, lo, hi = (ctypes.c_int * 2)(0, 0), (ctypes.c_float * 2)(0.0, 0.0), (ctypes.c_float * 2)(1.0, 1.0)
+    n = run.params.numel()
+    calls = {
+        'pinn_optim_step_at': lambda: lib.pinn_optim_step_at(_ptr(run.params), _ptr(run.grads), _ptr(run.m), _ptr(run.v), _ptr(run.mask), n,
+                                                             _ptr(run.step), 1, ctypes.byref(optim), _ptr(run.losses), run.net.layout.off_loss, None),
+        'pinn_residual_optim_step': lambda: lib.pinn_residual_optim_step(
+            run.net.handle, ctypes.byref(run.residual), _ptr(run.params), _ptr(run.xs), BATCH, dirs, ND, N2, None, 0.0, _ptr(run.grads), _ptr(run.m),
+            _ptr(run.v), _ptr(run.mask), _ptr(run.step), 1, ctypes.byref(optim), _ptr(run.losses), _ptr(run.ws), run.ws_bytes, None),
+        'pinn_fit_steps': lambda: lib.pinn_fit_steps(
+            run.net.handle, ctypes.byref(run.residual), _ptr(run.params), _ptr(run.xs), BATCH, kind, lo, hi, SEED, 0, dirs, ND, N2, 0.0, _ptr(run.grads),
+            _ptr(run.m), _ptr(run.v), _ptr(run.mask), _ptr(run.step), 1, ctypes.byref(optim), _ptr(run.losses), 2, _ptr(run.ws), run.ws_bytes,
+            _ptr(run.ctrl), run.ctrl.numel(), None, None)}
+    for name, call in calls.items():
+        assert call() != 0, name
+        assert ('beta' if 'betas' in bad else 'epsilon') in lib.pinn_last_error().decode(), name
+        _same(run.state(), before, name)
+    optim.beta2, optim.eps = 0.999, 1e-8            # (the same calls with torch's numbers go through: the refusals were about the numbers)
+    for name, call in calls.items():
+        assert call() == 0, (name, lib.pinn_last_error().decode())

@@ -346,7 +346,7 @@ def test_criterion_fields_of_the_residual_struct_on_the_gpu():
 
 # ---- 4. / 5. one-launch forms: L1 after MSE on one net, chunks against the eager loop ----------------------------------------------------
 def _l1_after_mse_case(pa, extra, lib, monkeypatch, name, batch, niters, persist, exact):
-    """ Solver.fit(MSE) then Solver.fit(L1) on ONE net, every chunk through pinn_fit_steps_graph, against the per-iteration loop on the same
+    """ Solver.fit(MSE) then Solver.fit(L1) on ONE net, every chunk through pinn_fit_steps with a control block, against the per-iteration loop on the same
     Philox batches: a launch graph (or one-CU chunk) recorded for MSE must not be replayed for L1. Rule of the existing chunk tests: launch
     graphs bit for bit (test_gpu_parity.test_fit_chunks_as_launch_graphs_follow_the_eager_loop_bit_for_bit), the one-launch kernel to fp32
     round-off (test_emu_engine._one_launch_case). """
@@ -357,7 +357,7 @@ def _l1_after_mse_case(pa, extra, lib, monkeypatch, name, batch, niters, persist
         cfg, solver = make_solver(name, pa, **extra)
         solver.set_criterion_path('fused')
         if not chunks:
-            solver._device_columns = lambda sampler: None          # the per-iteration loop (pinn_residual_adam_step)
+            solver._device_columns = lambda sampler: None          # the per-iteration loop (pinn_residual_optim_step)
         st0 = (ctypes.c_int32 * 4)()
         lib.pinn_debug_fit_graph_stats(st0)
         solver.fit(niters=niters, batch_size=batch, lr=0.005)
@@ -382,7 +382,7 @@ def _l1_after_mse_case(pa, extra, lib, monkeypatch, name, batch, niters, persist
 
 
 def test_l1_after_mse_through_the_chunk_entry_point_eager_fallback(pa, emu_lib, monkeypatch):
-    """ the emulator refuses capture: pinn_fit_steps_graph runs its eager loop, which must honour the criterion """
+    """ the emulator refuses capture: pinn_fit_steps with a control block runs its eager loop, which must honour the criterion """
     monkeypatch.setattr(pa.Solver, 'FIT_CTRL_ON_HOST', True)
     _l1_after_mse_case(pa, emu_kwargs(emu_lib), emu_lib, monkeypatch, 'cfg4', 40, 5, 0, True)
 
@@ -441,7 +441,7 @@ def _one_cu_l1_case(pa, extra, lib, monkeypatch, niters):
         solver.set_criterion_path('fused')
         sampler, _ = _one_cu_batches(pa, ONE_CU_SEEDS[niters], 0)
         if not chunks:
-            solver._device_columns = lambda sampler: None          # the per-iteration loop (pinn_residual_adam_step)
+            solver._device_columns = lambda sampler: None          # the per-iteration loop (pinn_residual_optim_step)
         st0 = (ctypes.c_int32 * 4)()
         lib.pinn_debug_fit_graph_stats(st0)
         solver.fit(niters=niters, batch_size=100, sampler=sampler, lr=0.005)

@@ -118,7 +118,8 @@ def test_rules_match_torch_optim_on_the_gpu(pa, name, kw):
 
 
 def _plain_adam_case(pa, lib, device, n):
-    """ plain Adam() through the family's entry points is the Adam entry points' update, bit for bit (both standalone forms) """
+    """ plain Adam() as torch resolves it (FlatOptimizer.hyper) is `Net.adam_step`'s struct of the bare numbers: the same update, bit for bit
+    (both standalone forms) """
     engine = pa.engine
     torch.manual_seed(1)
     net = engine.Net([2, 16, 1], 'tanh', 2, lib=lib)
@@ -461,8 +462,8 @@ def _chunk_run(pa, extra, lib, monkeypatch, opt, niters, graph, persist, eager_l
 
 
 def _graph_case(pa, extra, lib, monkeypatch, opt, niters):
-    """ the chunks through pinn_fit_steps_optim_graph (launch graphs on the device; the emulator refuses capture and runs the entry point's
-    eager loop) against pinn_fit_steps_optim: the same kernels with the same arguments -- every loss, parameter and both state arrays equal """
+    """ the chunks through pinn_fit_steps with a control block (launch graphs on the device; the emulator refuses capture and runs the entry
+    point's eager loop) against pinn_fit_steps without one: the same kernels with the same arguments -- every loss, parameter and both state arrays equal """
     a = _chunk_run(pa, extra, lib, monkeypatch, opt, niters, False, 0)
     b = _chunk_run(pa, extra, lib, monkeypatch, opt, niters, True, 0)
     assert a['t'] == b['t'] == a['host_t'] == b['host_t'] == sum(niters)
@@ -537,7 +538,7 @@ def _interrupted_case(pa, extra, monkeypatch):
 
     def stopping(*args, **kw):
         args = list(args)
-        args[17] = 3                                            # k_steps: the library applies three of the six iterations ...
+        args[15] = 3                                            # k_steps: the library applies three of the six iterations ...
         real(*args, **kw)
         raise KeyboardInterrupt                                 # ... and the call does not come back
     monkeypatch.setattr(solver.model.net, 'fit_steps', stopping)
@@ -640,20 +641,33 @@ def _abi_case(pa, lib, device):
 
     def buffers():
         return start.clone(), torch.zeros_like(start), torch.zeros_like(start), torch.zeros(1, dtype=torch.int32, device=device)
-    # a zeroed struct with Adam's four numbers is plain Adam: pinn_adam_step_at, bit for bit
+    # a zeroed struct with Adam's four numbers is plain Adam: torch.optim.Adam's update, restated here in fp64 on the numbers the struct
+    # carries (floats) -- and the same bits as the struct Optim.build makes of those numbers with everything else at its default
     zeroed = engine.Optim()
     assert (zeroed.rule, zeroed.weight_decay, zeroed.momentum, zeroed.dampening, zeroed.alpha, zeroed.nesterov, zeroed.centered) == (0, 0, 0, 0, 0, 0, 0)
     zeroed.lr, zeroed.beta1, zeroed.beta2, zeroed.eps = 0.01, 0.9, 0.999, 1e-8
+    built = engine.Optim.build(engine.OPT_ADAM, 0.01, betas=(0.9, 0.999), eps=1e-8)
     p0, m0, v0, s0 = buffers()
     p1, m1, v1, s1 = buffers()
     loss0, loss1 = torch.zeros(1, device=device), torch.zeros(1, device=device)
+    live = mask.bool().cpu().numpy()
+    g64 = grad.double().cpu().numpy()
+    p64, m64, v64 = start.double().cpu().numpy().copy(), np.zeros(n), np.zeros(n)
+    lr, b1, b2, eps = float(zeroed.lr), float(zeroed.beta1), float(zeroed.beta2), float(zeroed.eps)
     for step in (1, 2, 3):
-        assert lib.pinn_adam_step_at(vp(p0), vp(grad), vp(m0), vp(v0), vp(mask), n, vp(s0), step, 0.01, 0.9, 0.999, 1e-8, vp(loss0), 7,
-                                     engine.stream_of(p0)) == 0
+        assert lib.pinn_optim_step_at(vp(p0), vp(grad), vp(m0), vp(v0), vp(mask), n, vp(s0), step, ctypes.byref(built), vp(loss0), 7,
+                                      engine.stream_of(p0)) == 0
         assert lib.pinn_optim_step_at(vp(p1), vp(grad), vp(m1), vp(v1), vp(mask), n, vp(s1), step, ctypes.byref(zeroed), vp(loss1), 7,
                                       engine.stream_of(p1)) == 0
+        m64[live] += (1 - b1) * (g64[live] - m64[live])
+        v64[live] = b2 * v64[live] + (1 - b2) * g64[live] ** 2
+        p64[live] -= lr / (1 - b1 ** step) * m64[live] / (np.sqrt(v64[live]) / np.sqrt(1 - b2 ** step) + eps)
     assert torch.equal(p0, p1) and torch.equal(m0, m1) and torch.equal(v0, v1) and int(s0) == int(s1) == 3
     assert float(loss1) == float(grad[7]) == float(loss0) and not torch.equal(p1, start)
+    # (three steps of at most a handful of fp32 roundings each, 6e-8 apiece, on values that do not cancel: the bound of the rule test)
+    for got, want in ((p1, p64), (m1, m64), (v1, v64)):
+        assert rel_l2(got.cpu().numpy().astype(np.float64), want) < 1e-6
+    assert torch.equal(p1[~mask.bool()], start[~mask.bool()]) and not m1[~mask.bool()].any() and not v1[~mask.bool()].any()
     # refusals: non-zero, a message, nothing launched
     build = engine.Optim.build
     bad = [build(4, 0.01), build(-1, 0.01), build(engine.OPT_ADAMW, 0.01, betas=(0.9, 0.999), eps=1e-8, weight_decay=-0.01),
@@ -689,10 +703,9 @@ def _abi_case(pa, lib, device):
         step = torch.zeros(1, dtype=torch.int32, device=device)
         history = torch.zeros(4, device=device)
         with pytest.raises(RuntimeError, match='optimizer'):
-            net.residual_adam_step(res, flat, xs, grads, ws, m, v, fmask, step, 1, 0.01, dir_cols=(0, 1), n2=2, optim=optim)
+            net.residual_optim_step(res, flat, xs, grads, ws, m, v, fmask, step, 1, optim, dir_cols=(0, 1), n2=2)
         with pytest.raises(RuntimeError, match='optimizer'):
-            net.fit_steps(res, flat, xs, [(0, 0.0, 1.0)] * 2, 5, 0, grads, ws, m, v, fmask, step, 1, 0.01, (0.9, 0.999), 1e-8, history, 4,
-                          dir_cols=(0, 1), n2=2, optim=optim)
+            net.fit_steps(res, flat, xs, [(0, 0.0, 1.0)] * 2, 5, 0, grads, ws, m, v, fmask, step, 1, optim, history, 4, dir_cols=(0, 1), n2=2)
         assert torch.equal(flat, keep) and not grads.any() and not m.any() and int(step) == 0 and not history.any()
     # a good one: the fused iteration is the plain step followed by the standalone update
     optim = build(engine.OPT_SGD, 0.01, momentum=0.9, weight_decay=0.01)
@@ -701,7 +714,7 @@ def _abi_case(pa, lib, device):
     ma, va, mb, vb = (torch.zeros_like(flat) for _ in range(4))
     sa, sb = (torch.zeros(1, dtype=torch.int32, device=device) for _ in range(2))
     for step in (1, 2, 3):
-        net.residual_adam_step(res, a, xs, ga, ws, ma, va, fmask, sa, step, 0.01, dir_cols=(0, 1), n2=2, optim=optim)
+        net.residual_optim_step(res, a, xs, ga, ws, ma, va, fmask, sa, step, optim, dir_cols=(0, 1), n2=2)
         net.residual_step(res, b, xs, gb, ws, dir_cols=(0, 1), n2=2)
         net.optim_step(b, gb, mb, vb, fmask, sb, optim, at=step)
     # (two kernels around one expression tree: the bound of the rule test, not bits)

@@ -1147,7 +1147,7 @@ def test_sin_net_of_depth_four_on_the_static_kernel(pa):
 
 @pytest.mark.parametrize('name,batch', [('cfg1', 100), ('cfg4', 2048)])
 def test_fit_chunks_as_launch_graphs_follow_the_eager_loop_bit_for_bit(pa, name, batch, monkeypatch):
-    """ Solver.fit at small batches replays every 128-iteration chunk as ONE launch graph (pinn_fit_steps_graph: the Philox batch
+    """ Solver.fit at small batches replays every 128-iteration chunk as ONE launch graph (pinn_fit_steps with a control block: the Philox batch
     counter, the Adam step with its bias corrections and the loss slot come from a device control block); the trajectory -- every loss,
     every parameter, the Adam state -- must be the eager loop's, bit for bit, across several chunks and a second fit that continues """
     def run(graph):

@@ -1,6 +1,6 @@
 """ Learning-rate schedules in `Solver.fit` (`lr_scheduler=`, `lr_scheduler_kwargs=`): torch's own scheduler objects compute every rate on the
 host; the rates reach the kernels per iteration -- by value on the eager paths, through the control block of the fit chunks (include/pinn.h
-pinn_fit_steps_optim_sched), whose launch graph and one-CU kernel go on running while the rate changes under them. CPU tier on the emulator
+lr_steps of pinn_fit_steps), whose launch graph and one-CU kernel go on running while the rate changes under them. CPU tier on the emulator
 build of the product sources, `-m gpu` twins on the device.
 
 Tolerances are the suite's own. Chunk forms against the per-iteration calls: the eager chunk and the launch-graph chunk bit for bit, the
@@ -87,7 +87,7 @@ def rate_table(k, scale=1.0):
 
 
 def _contract_run(pa, extra, monkeypatch, rule, tables, form):
-    """ cfg1 at batch 100 on buffers of the test's own. form: 'steps' -- sample_points + residual_adam_step(optim=...) per iteration with the
+    """ cfg1 at batch 100 on buffers of the test's own. form: 'steps' -- sample_points + residual_optim_step per iteration with the
     rate in the struct; 'eager' -- fit_steps(lr_steps=) without a control block; 'graph' / 'one_cu' -- with one, the narrow net's one-launch
     form off / on """
     from pydens_amd.solver import FlatOptimizer
@@ -121,11 +121,11 @@ def _contract_run(pa, extra, monkeypatch, rule, tables, form):
             for j, rate in enumerate(table):
                 net.sample_points(xs, columns, seed, at + j)
                 optim.lr = rate
-                net.residual_adam_step(solver.program, flat, xs, solver.grads, ws, m, v, mask, step, at + j + 1, 0.0,
-                                       loss_out=history.data_ptr() + 4 * (at + j), optim=optim, **common)
+                net.residual_optim_step(solver.program, flat, xs, solver.grads, ws, m, v, mask, step, at + j + 1, optim,
+                                        loss_out=history.data_ptr() + 4 * (at + j), **common)
         else:
-            net.fit_steps(solver.program, flat, xs, columns, seed, at, solver.grads, ws, m, v, mask, step, at + 1, LR, (0.0, 0.0), 0.0,
-                          history[at:at + k], k, ctrl=ctrl, optim=optim, lr_steps=table, **common)
+            net.fit_steps(solver.program, flat, xs, columns, seed, at, solver.grads, ws, m, v, mask, step, at + 1, optim,
+                          history[at:at + k], k, ctrl=ctrl, lr_steps=table, **common)
         at += k
     st = _stats(net.lib)
     return dict(params=flat.detach().clone(), m=m, v=v, step=step.clone(), losses=history, kernel=net.lib.pinn_last_kernel_name().decode(),

@@ -222,7 +222,7 @@ BATCH, NITERS = 700, 5          # more points than one block of the reduction ha
 
 def _next_batch_case(pa, lib, extra, monkeypatch):
     """ config 1 through the chunk entry point (pinn_fit_steps: from the second iteration on the reduction's tail draws the batch) against
-    the per-iteration loop (pinn_sample_points + pinn_residual_adam_step): the same trajectory, and the batch left in the buffer is the
+    the per-iteration loop (pinn_sample_points + pinn_residual_optim_step): the same trajectory, and the batch left in the buffer is the
     one pinn_sample_kernel draws for that call """
     monkeypatch.setenv('PYDENS_AMD_FIT_GRAPH', '0')
     monkeypatch.setenv('PYDENS_AMD_FIT_PERSIST', '0')          # (the tile kernel + reduction form, not the one-launch chunk)

@@ -25,8 +25,8 @@ history = torch.zeros(K, device='cuda')
 
 def chunk(stream=None):
     model.net.fit_steps(solver.program, model.flat, xs, columns, 1234, 0, solver.grads, ws, adam.exp_avg, adam.exp_avg_sq, adam.mask,
-                        adam.step_count, 1, adam.lr, adam.betas, adam.eps, history, K, dir_cols=spec.dir_cols, n2=n2,
-                        ic_const=model.kernel_ic_const(), stream=stream)
+                        adam.step_count, 1, adam.optim, history, K, dir_cols=spec.dir_cols, n2=n2, ic_const=model.kernel_ic_const(),
+                        stream=stream)
 
 
 def timed(fn):
