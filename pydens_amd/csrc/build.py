@@ -100,11 +100,7 @@ def _build(force, verbose, extra_flags, widths):
     jobs = []
     for hp in WIDTHS:
         obj = os.path.join(OBJ, f'inst_hp{hp}.o')
-        if hp not in widths:
-            extra = ['-DPINN_INST_STUB']
-        else:
-            extra = []
-        jobs.append((obj, [hipcc, *FLAGS, *WIDTH_FLAGS.get(hp, []), *extra_flags, *extra, f'-DPINN_INST_HP={hp}', '-c',
+        jobs.append((obj, [hipcc, *FLAGS, *WIDTH_FLAGS.get(hp, []), *extra_flags, f'-DPINN_INST_HP={hp}', '-c',
                            os.path.join(HERE, 'pinn_inst.inc'), '-o', obj]))
     # second set of full breadth kernels (round 5: all sixteen activations, nested skips -- pinn_inst.inc PINN_INST_ALLACT): a unit of
     # its own per width, so that the build's wall time stays that of its longest unit

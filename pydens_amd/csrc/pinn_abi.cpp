@@ -106,8 +106,8 @@ struct pinn_net {
 };
 
 namespace {
-typedef int (*launch_fn)(int, int, const PinnKArgs*, int, void*, int, long long*);
-typedef int (*wgrad_fn)(int, int, int, int, const PinnKArgs*, int, void*, int, long long*);
+typedef int (*launch_fn)(int, int, const PinnKArgs*, const PinnLaunchReq&);
+typedef int (*wgrad_fn)(int, int, int, int, const PinnKArgs*, const PinnLaunchReq&);
 
 wgrad_fn wgrad_launcher_for(int hp) {
     switch (hp) {
@@ -215,36 +215,34 @@ int make_plan(const pinn_net* net, int64_t n_points, int nd, int n2, Plan* plan,
     probe.mode = mode;
     probe.res_kind = res_kind;
     probe.comb = comb;
-    long long info[16] = {0, 0, 0, 1, 1, 0, 0, 0, 0, 0, 1, 0, 0, 0, 0, 0};
-    if (plan->fn(nd, plan->n2k, &probe, 0, nullptr, 1, info))
+    PinnLaunchInfo info, winfo;
+    if (plan->fn(nd, plan->n2k, &probe, {PinnLaunchOp::Plan, 0, nullptr, &info}))
         return fail("no kernel instantiation for width %d with nd=%d n2=%d%s", net->lay.hp, nd, plan->n2k, comb ? " (combined)" : "");
-    plan->smem = (size_t)info[0];
-    plan->threads = (int)info[1];
-    plan->slab_vec4_per_wg = (size_t)info[2];
-    plan->wt_floats_per_wg = (size_t)info[5];
+    plan->smem = (size_t)info.smem_bytes;
+    plan->threads = info.threads;
+    plan->slab_vec4_per_wg = (size_t)info.slab_vec4_per_wg;
+    plan->wt_floats_per_wg = (size_t)info.wt_floats_per_wg;
     const int64_t ntiles = (n_points + 15) / 16;
-    const int64_t wg_tiles = (ntiles + info[4] - 1) / info[4];       // a two-team workgroup streams two tiles at a time
-    if (info[3] > net->max_per_cu) info[3] = net->max_per_cu;
-    plan->per_cu = (int)info[3];
-    int64_t grid = (int64_t)device_cus(net) * info[3];
-    const int64_t teams = info[10] > 0 ? info[10] : 1;              // a two-team workgroup streams two tiles at a time
+    const int64_t wg_tiles = (ntiles + info.mt - 1) / info.mt;
+    plan->per_cu = info.per_cu > net->max_per_cu ? net->max_per_cu : info.per_cu;
+    int64_t grid = (int64_t)device_cus(net) * plan->per_cu;
+    const int64_t teams = info.teams > 0 ? info.teams : 1;          // a two-team workgroup streams two tiles at a time
     if (grid > (wg_tiles + teams - 1) / teams) grid = (wg_tiles + teams - 1) / teams;
     if (grid < 1) grid = 1;
     plan->grid = (int)grid;
     plan->ntiles = wg_tiles;
-    plan->mt = (int)info[4];
+    plan->mt = info.mt;
     plan->comb = comb;
-    plan->wgx = (mode != PINN_MODE_FORWARD && info[6]) ? 1 : 0;
-    plan->wt_global = (int)info[9];
-    plan->split = (int)info[11];
-    plan->prepass_floats_per_lane = (int)info[12];
+    plan->wgx = (mode != PINN_MODE_FORWARD && info.wgx) ? 1 : 0;
+    plan->wt_global = info.wt_global;
+    plan->split = info.split;
+    plan->prepass_floats_per_lane = info.prepass_floats_per_lane;
     plan->grid2 = 0; plan->wfn = nullptr; plan->gz_vec4_per_tile = 0; plan->chunk_tiles = wg_tiles;
     if (plan->wgx) {
         plan->wfn = wgrad_launcher_for(net->lay.hp);
-        long long winfo[12] = {0, 0, 0, 1, 1, 0, 0, 0, 0, 0, 1, 0};
-        if (!plan->wfn || plan->wfn(nd, plan->n2k, comb, plan->mt, &probe, 0, nullptr, 1, winfo))
+        if (!plan->wfn || plan->wfn(nd, plan->n2k, comb, plan->mt, &probe, {PinnLaunchOp::Plan, 0, nullptr, &winfo}))
             return fail("no weight-gradient kernel for width %d with nd=%d n2=%d%s", net->lay.hp, nd, plan->n2k, comb ? " (combined)" : "");
-        int64_t grid2 = (int64_t)device_cus(net) * winfo[3];
+        int64_t grid2 = (int64_t)device_cus(net) * winfo.per_cu;
         if (grid2 > wg_tiles) grid2 = wg_tiles;
         plan->grid2 = (int)(grid2 < 1 ? 1 : grid2);
         // the hidden->hidden blocks of a partial row are written by pinn_wgrad_kernel alone (rows < grid2; the tile kernel leaves
@@ -252,7 +250,7 @@ int make_plan(const pinn_net* net, int64_t n_points, int nd, int n2, Plan* plan,
         // rows whose blocks nobody wrote -- the occupancy query may answer more workgroups per CU for the tile
         // kernel than WGS_PER_CU of the weight-gradient kernel, so the tile grid is capped here
         if (plan->grid > plan->grid2) plan->grid = plan->grid2;
-        plan->gz_vec4_per_tile = (size_t)info[7];
+        plan->gz_vec4_per_tile = (size_t)info.gz_vec4_per_tile;
         // whole sweeps of the persistent workgroups per chunk
         const size_t per_tile = (plan->slab_vec4_per_wg + plan->gz_vec4_per_tile) * 16;
         const int64_t sweep = plan->grid2 > plan->grid ? plan->grid2 : plan->grid;
@@ -787,6 +785,7 @@ int pinn_destroy(pinn_t* net) {
 #ifndef PINN_EMU
     if (net && net->fit_graph_exec) (void)hipGraphExecDestroy((hipGraphExec_t)net->fit_graph_exec);
 #endif
+    g_fit_last_sync = nullptr;          // (the flag lived in a workspace of this net's calls)
     delete net;
     return 0;
 }
@@ -860,7 +859,7 @@ static int jet_forward_impl(pinn_t* net, const float* params, const float* xs, i
         a.slab = reinterpret_cast<f32x4*>(workspace);
     }
     set_tile_range(&a, plan, 0, plan.ntiles);
-    const int rc = plan.fn(nd, plan.n2k, &a, plan.grid, stream, 0, nullptr);
+    const int rc = plan.fn(nd, plan.n2k, &a, {PinnLaunchOp::Launch, plan.grid, stream});
     note_launch(plan);
     return rc ? fail("tile kernel launch failed (%d)", rc) : 0;
 }
@@ -953,14 +952,14 @@ static int run_train(pinn_t* net, PinnKArgs* a, const Plan& plan, int nd, float*
         // (virtual workgroups, no device-scope wait) for batches of at most fit_onecu_rounds sweeps of its virtual workgroups; mode 1:
         // the grid form (every workgroup resident).
         tail->persist->launched = false;
-        long long has[3] = {0, 0, 0};
+        PinnFitProbe has;
         const size_t pc = (size_t)net->lay.p_total;
         bool ok = !plan.wgx && !plan.wt_global && !plan.split && plan.chunk_tiles >= plan.ntiles && !g_profile &&
-                  (!aux_bytes || a->pre.n_ops > 0) && plan.fn(nd, plan.n2k, a, plan.grid, stream, 3, has) == 0 && has[0];
+                  (!aux_bytes || a->pre.n_ops > 0) && plan.fn(nd, plan.n2k, a, {PinnLaunchOp::FitProbe, plan.grid, stream, nullptr, &has}) == 0 && has.carries;
         // (pre-pass rows: only where the pre-pass went INTO the kernel above, which then evaluates it for every batch it draws. One that
         //  took the separate pinn_aux_kernel launch -- switched off, or more double registers than prepass_floats_per_lane holds -- wrote
         //  the rows of the batch in `xs` once: the chunk keeps the launch graphs or the eager loop, which run it every iteration)
-        const int vw = (int)has[1];
+        const int vw = has.onecu_vw;
         const bool onecu = ok && net->fit_persistent == 2 && vw >= 2 && vw <= 8 && plan.ntiles <= (int64_t)vw * net->fit_onecu_rounds;
         const bool gridform = ok && net->fit_persistent == 1 && plan.grid <= PINN_FIT_MAX_WGS;
         const int rows = onecu ? vw : plan.grid, states = onecu ? 1 : plan.grid;
@@ -980,20 +979,20 @@ static int run_train(pinn_t* net, PinnKArgs* a, const Plan& plan, int nd, float*
             if (!onecu && hipMemsetAsync(P.sync, 0, 256, (hipStream_t)stream) != hipSuccess) return fail("hipMemsetAsync failed");
 #endif
             set_tile_range(a, plan, 0, plan.ntiles);
-            const int rc = plan.fn(nd, plan.n2k, a, onecu ? 1 : plan.grid, stream, onecu ? 4 : 2, reinterpret_cast<long long*>(&P));
+            const int rc = plan.fn(nd, plan.n2k, a, {onecu ? PinnLaunchOp::FitOneCu : PinnLaunchOp::FitGrid, onecu ? 1 : plan.grid, stream, nullptr, nullptr, &P});
             note_launch(plan);
             if (rc == 1) return 0;               // (this instantiation has no such form after all: the caller falls back)
             if (rc) return fail("fit kernel launch failed (%d)", rc);
             tail->persist->launched = true;
             if (onecu) {
                 // pinn_last_launch_info: ONE workgroup of vw virtual ones, and the LDS it asked for (PinnFitVw: the blocks and W^T of
-                // query 3, then state, rows, batch and pre-pass rows as in resident_floats)
+                // the probe, then state, rows, batch and pre-pass rows as in resident_floats)
                 const long long pcp = ((long long)pc + 3) / 4 * 4, n = a->n_points;
                 const long long resident = (3 + vw) * pcp + (n * a->d + 3) / 4 * 4 + (n * a->n_aux + 3) / 4 * 4;
                 g_pinn_last_launch[0] = 1; g_pinn_last_launch[1] = 1;
-                g_pinn_last_launch[2] = plan.threads * vw; g_pinn_last_launch[3] = (int)(has[2] + 4 * resident);
+                g_pinn_last_launch[2] = plan.threads * vw; g_pinn_last_launch[3] = (int)(has.onecu_base_bytes + 4 * resident);
             }
-            g_fit_last_sync = onecu ? nullptr : P.sync;        // (grid form: its timeout flag, read back by pinn_fit_chunk_status)
+            if (!onecu) g_fit_last_sync = P.sync;               // (grid form: its timeout flag, read back by pinn_fit_chunk_status)
         }
         return 0;
     }
@@ -1005,7 +1004,7 @@ static int run_train(pinn_t* net, PinnKArgs* a, const Plan& plan, int nd, float*
 #ifndef PINN_EMU
         if (pe) hipEventRecord(pe->tile0, (hipStream_t)stream);
 #endif
-        const int rc = plan.fn(nd, plan.n2k, a, plan.grid, stream, 0, nullptr);
+        const int rc = plan.fn(nd, plan.n2k, a, {PinnLaunchOp::Launch, plan.grid, stream});
         note_launch(plan);
         if (rc) return fail("tile kernel launch failed (%d)", rc);
 #ifndef PINN_EMU
@@ -1015,7 +1014,7 @@ static int run_train(pinn_t* net, PinnKArgs* a, const Plan& plan, int nd, float*
 #ifndef PINN_EMU
             if (pe) hipEventRecord(pe->wg0, (hipStream_t)stream);
 #endif
-            const int rw = plan.wfn(nd, plan.n2k, plan.comb, plan.mt, a, plan.grid2, stream, 0, nullptr);
+            const int rw = plan.wfn(nd, plan.n2k, plan.comb, plan.mt, a, {PinnLaunchOp::Launch, plan.grid2, stream});
             if (rw) return fail("weight-gradient kernel launch failed (%d)", rw);
 #ifndef PINN_EMU
             if (pe) { hipEventRecord(pe->wg1, (hipStream_t)stream); pe->have_wgrad = true; }
@@ -1259,6 +1258,7 @@ static int launch_fit_ctrl(const FitCall& f) {
 static int try_one_launch_chunk(const FitCall& f, bool* launched) {
     const pinn_net* net = f.step.net;
     *launched = false;
+    g_fit_last_sync = nullptr;          // (a chunk that declines, or takes the one-CU form, leaves no flag of an earlier call behind)
     OneLaunch one;
     memset(&one, 0, sizeof(one));
     PinnNextBatch spec_probe = {nullptr, 0, {}, 0u, 0u, 0ull};

@@ -50,7 +50,7 @@ struct PinnFitP {
 template <int HP, int ND, int N2, int MT, int LHC, int VAR>
 struct PinnFitVw {
     using C = PinnCfg<HP, ND, N2, MT, false>;
-    static constexpr int BLOCK = (((VAR >> 4) & 3) != 0) ? C::TEAM_FLOATS : C::SMEM_FLOATS;
+    static constexpr int BLOCK = (pinn_var_spec(VAR) != 0) ? C::TEAM_FLOATS : C::SMEM_FLOATS;
     static constexpr int WT = C::wt_fits(LHC) ? LHC * HP * C::WT_LD : 0;
     static constexpr int PC_EST = HP * 8 + HP + (LHC > 2 ? LHC : 2) * (HP * HP + HP) + HP + 16;
     static constexpr int BY_WAVES = 8 / C::NW;
@@ -83,9 +83,9 @@ PINN_DEVICE unsigned pinn_fit_arrive_and_wait(unsigned* sync, unsigned target) {
 template <int HP, int ND, int N2, int MT, int LHC, int ACTC, bool COMB, int VAR, int VW>
 PINN_GLOBAL void PINN_LAUNCH_BOUNDS2((PinnCfg<HP, ND, N2, MT>::NTHREADS * VW), 2)
 pinn_fit_kernel(const PinnKArgs A0, const PinnFitP P) {
-    using C = PinnCfg<HP, ND, N2, MT, (VAR & 512) != 0>;
+    using C = PinnCfg<HP, ND, N2, MT, (VAR & PINN_VAR_SPLIT) != 0>;
     constexpr int NTH1 = C::NTHREADS, NTH = NTH1 * VW, T = C::T;
-    static_assert(HP <= 32 && !(VAR & (2 | 64 | 128 | 256 | 512)), "the one-launch fit chunk is built for the narrow nets (no streamed weight gradients)");
+    static_assert(HP <= 32 && !(VAR & (PINN_VAR_2WG | PINN_VAR_SLAB_LDS | PINN_VAR_WGX | PINN_VAR_TEAMS2 | PINN_VAR_SPLIT)), "the one-launch fit chunk is built for the narrow nets (no streamed weight gradients)");
     const int gtid = PINN_TID, bid = PINN_BID, G = PINN_NBLK;
     const int tid1 = gtid % NTH1, vbid = bid * VW + gtid / NTH1, R = G * VW;       // R partial rows: one per (virtual) workgroup
     const int pc = A0.p_core;

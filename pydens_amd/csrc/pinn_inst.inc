@@ -55,39 +55,55 @@ static inline bool pinn_needs_allact(const PinnKArgs* a) {
 #define PINN_CAT2(a, b) a##b
 #define PINN_CAT(a, b) PINN_CAT2(a, b)
 // (second set of full breadth kernels, defined in the -DPINN_INST_ALLACT=1 unit of this width: below)
-int PINN_CAT(pinn_launch_breadth2_hp, PINN_INST_HP)(int nd, int n2, int comb, const PinnKArgs* a, int grid, void* stream, int query, long long* info);
-int PINN_CAT(pinn_launch_wgrad2_hp, PINN_INST_HP)(int nd, int n2, int comb, const PinnKArgs* a, int grid, void* stream, int query, long long* info);
+int PINN_CAT(pinn_launch_breadth2_hp, PINN_INST_HP)(int nd, int n2, int comb, const PinnKArgs* a, const PinnLaunchReq& req);
+int PINN_CAT(pinn_launch_wgrad2_hp, PINN_INST_HP)(int nd, int n2, int comb, const PinnKArgs* a, const PinnLaunchReq& req);
+
+// plain activations: every layer Tanh or Sigmoid (the one-bit run-time code of the kernels without the breadth bit)
+static inline bool pinn_plain_acts(const PinnKArgs* a) {
+    for (int i = 0; i <= a->lh; ++i)
+        if (pinn_act_code(a->act_codes, i) >= 2) return false;
+    return true;
+}
 
 namespace {
-#ifndef PINN_EMU
-// dynamic-LDS attribute of a kernel: set once per (instantiation, device) -- a process may drive several devices
-inline int pinn_set_smem_attr(const void* fn, size_t smem, unsigned long long& done_mask) {
+// one kernel launch: the dynamic-LDS attribute (`smem_attr` bytes) set once per (kernel, device) -- a process may drive several
+// devices --, the launch, the error check; the emulator runs the kernel in place
+template <auto K, class... Args>
+int pinn_launch_kernel(int grid, int threads, size_t smem, size_t smem_attr, void* stream, const Args&... args) {
+#ifdef PINN_EMU
+    (void)smem_attr; (void)stream;
+    emu::launch(grid, threads, smem, [&] { K(args...); });
+    return 0;
+#else
+    static unsigned long long done_mask = 0;
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess || dev < 0) return 2;
     const unsigned long long bit = 1ull << (dev & 63);
     if (!(done_mask & bit)) {
-        if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) != hipSuccess) return 2;
+        if (hipFuncSetAttribute(reinterpret_cast<const void*>(K), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem_attr) != hipSuccess) return 2;
         done_mask |= bit;
     }
-    return 0;
-}
+    hipLaunchKernelGGL(K, dim3(grid), dim3(threads), smem, (hipStream_t)stream, args...);
+    return hipGetLastError() == hipSuccess ? 0 : 2;
 #endif
+}
 
 template <int ND, int N2, int LHC = -1, int ACTC = -1, int MT = 1, bool COMB = false, int VAR = 0>
-int launch_one(const PinnKArgs* a, int grid, void* stream, int query, long long* info) {
-    using C = PinnCfg<PINN_INST_HP, ND, N2, MT, (VAR & 512) != 0>;
-    constexpr int TEAMS = (VAR & 256) ? 2 : 1;                 // two tile streams in one 8-wave workgroup
+int launch_one(const PinnKArgs* a, const PinnLaunchReq& req) {
+    using C = PinnCfg<PINN_INST_HP, ND, N2, MT, (VAR & PINN_VAR_SPLIT) != 0>;
+    constexpr int TEAMS = (VAR & PINN_VAR_TEAMS2) ? 2 : 1;                 // two tile streams in one 8-wave workgroup
     constexpr int THREADS = C::NTHREADS * TEAMS;
-    constexpr size_t smem = (size_t)((VAR & 256) ? C::smem_floats_teams(LHC)
-                                     : (VAR & 64) ? C::slabl_smem_floats(LHC > 0 ? LHC : 1)
-                                     : ((VAR & 2) ? C::SMEM_FLOATS : C::smem_floats(LHC))) * sizeof(float);
+    constexpr size_t smem = (size_t)((VAR & PINN_VAR_TEAMS2) ? C::smem_floats_teams(LHC)
+                                     : (VAR & PINN_VAR_SLAB_LDS) ? C::slabl_smem_floats(LHC > 0 ? LHC : 1)
+                                     : ((VAR & PINN_VAR_2WG) ? C::SMEM_FLOATS : C::smem_floats(LHC))) * sizeof(float);
     static_assert(smem <= 160 * 1024, "LDS carve of this tile-kernel instantiation exceeds the 160 KB of a CU");
-    if (query == 1) {
-        info[0] = (long long)smem;
-        info[1] = THREADS;
-        info[2] = (long long)C::slab_vec4_per_wg(a->lh, (VAR & 8) ? a->n_skips * ((VAR & 128) ? 2 : 1) : 0) * TEAMS;
-        info[10] = TEAMS;
-        info[5] = (VAR & 64) ? (long long)a->lh * PINN_INST_HP * PINN_INST_HP : 0;     // per-workgroup W^T scratch (floats)
+    if (req.op == PinnLaunchOp::Plan) {
+        PinnLaunchInfo& info = *req.info;
+        info.smem_bytes = (long long)smem;
+        info.threads = THREADS;
+        info.slab_vec4_per_wg = (long long)C::slab_vec4_per_wg(a->lh, (VAR & PINN_VAR_BREADTH) ? a->n_skips * ((VAR & PINN_VAR_WGX) ? 2 : 1) : 0) * TEAMS;
+        info.teams = TEAMS;
+        info.wt_floats_per_wg = (VAR & PINN_VAR_SLAB_LDS) ? (long long)a->lh * PINN_INST_HP * PINN_INST_HP : 0;
         int per_cu = 1;
 #ifndef PINN_EMU
         // (asked once per instantiation: every step plans its launch, and the occupancy API is not free)
@@ -100,139 +116,99 @@ int launch_one(const PinnKArgs* a, int grid, void* stream, int query, long long*
         }
         per_cu = per_cu_cached;
 #endif
-        info[3] = per_cu;
-        info[4] = MT;
-        info[6] = (VAR & 128) ? 1 : 0;                                           // WGX: slab per TILE + gz slab + pinn_wgrad_kernel
-        info[7] = (VAR & 128) ? (long long)C::gz_vec4_per_tile(a->lh) : 0;
-        info[8] = COMB ? 1 : 0;
-        info[9] = ((C::WTG || (VAR & 2)) && !(VAR & 512)) ? 1 : 0;   // data-gradient GEMM reads the transposed GLOBAL copy of the hidden weights
-        info[11] = (VAR & 512) ? 1 : 0;                     // split-bf16 kernel: needs the fragment copy of the hidden weights (pinn_wsplit_kernel)
-        info[12] = C::PREPASS_FLOATS_PER_LANE;               // LDS floats per point of a tile for the in-kernel pre-pass's double registers
+        info.per_cu = per_cu;
+        info.mt = MT;
+        info.wgx = (VAR & PINN_VAR_WGX) ? 1 : 0;
+        info.gz_vec4_per_tile = (VAR & PINN_VAR_WGX) ? (long long)C::gz_vec4_per_tile(a->lh) : 0;
+        info.wt_global = ((C::WTG || (VAR & PINN_VAR_2WG)) && !(VAR & PINN_VAR_SPLIT)) ? 1 : 0;
+        info.split = (VAR & PINN_VAR_SPLIT) ? 1 : 0;
+        info.prepass_floats_per_lane = C::PREPASS_FLOATS_PER_LANE;
         return 0;
     }
+    if (req.op != PinnLaunchOp::Launch) {
 #if PINN_INST_HP <= 32
-    // the one-launch fit chunk (pinn_fit_kernel.h). query 3: info[0] = 1 if this instantiation carries it, info[1] = virtual workgroups of
-    // its one-CU form (0: none), info[2] = LDS bytes of that form. query 2: launch the grid form (`grid` resident workgroups, device-scope
-    // wait); query 4: launch the one-CU form (one hardware workgroup). `info` then carries a PinnFitP.
-    constexpr bool FITK = (VAR & (2 | 64 | 128 | 256 | 512)) == 0;
-    using FV = PinnFitVw<PINN_INST_HP, ND, N2, MT, LHC, VAR>;
-    // (not the second set of breadth kernels at width 32: with the state in LDS, hipcc 7.2 dies on one of them with "Illegal instruction
-    //  detected: V_CMP_NE_U32_e32 0, $src_shared_base" -- pinn_fit_kernel.h; those nets keep the launch graphs)
-    constexpr int FIT_VW = (FITK && FV::VW >= 2 && !(PINN_INST_HP == 32 && ACTC == -2)) ? FV::VW : 0;
-    if (query == 3) {
-        info[0] = FITK ? 1 : 0;
-        info[1] = FIT_VW;
-        info[2] = FIT_VW ? (long long)FV::BASE_FLOATS * 4 : 0;
-        return 0;
-    }
-    if (query == 2 || query == 4) {
+        // the one-launch fit chunk (pinn_fit_kernel.h): the grid form (`grid` resident workgroups, device-scope wait) and the one-CU
+        // form (one hardware workgroup of FIT_VW virtual ones)
+        constexpr bool FITK = (VAR & (PINN_VAR_2WG | PINN_VAR_SLAB_LDS | PINN_VAR_WGX | PINN_VAR_TEAMS2 | PINN_VAR_SPLIT)) == 0;
+        using FV = PinnFitVw<PINN_INST_HP, ND, N2, MT, LHC, VAR>;
+        // (not the second set of breadth kernels at width 32: with the state in LDS, hipcc 7.2 dies on one of them with "Illegal instruction
+        //  detected: V_CMP_NE_U32_e32 0, $src_shared_base" -- pinn_fit_kernel.h; those nets keep the launch graphs)
+        constexpr int FIT_VW = (FITK && FV::VW >= 2 && !(PINN_INST_HP == 32 && ACTC == -2)) ? FV::VW : 0;
+        if (req.op == PinnLaunchOp::FitProbe) {
+            *req.probe = {FITK ? 1 : 0, FIT_VW, FIT_VW ? (long long)FV::BASE_FLOATS * 4 : 0};
+            return 0;
+        }
         if constexpr (FITK) {
-            const PinnFitP* fp = reinterpret_cast<const PinnFitP*>(info);
-            if (query == 2) {
+            if (req.op == PinnLaunchOp::FitGrid) {
 #ifdef PINN_EMU
-                if (grid != 1) return 1;                    // (no device-scope wait in the emulator)
-                const PinnKArgs args = *a; const PinnFitP fargs = *fp;
-                emu::launch(1, THREADS, smem, [&] { pinn_fit_kernel<PINN_INST_HP, ND, N2, MT, LHC, ACTC, COMB, VAR, 1>(args, fargs); });
+                if (req.grid != 1) return 1;                    // (no device-scope wait in the emulator)
 #else
-                static unsigned long long fit_attr_done = 0;
-                if (pinn_set_smem_attr(reinterpret_cast<const void*>(&pinn_fit_kernel<PINN_INST_HP, ND, N2, MT, LHC, ACTC, COMB, VAR, 1>),
-                                       smem, fit_attr_done)) return 2;
                 // the device-scope arrive / wait of this form needs EVERY workgroup of the grid resident at once (ADVICE r5): asked, not
                 // assumed -- a grid beyond what the device holds declines (the caller keeps the launch graphs)
-                {
-                    static int fit_per_cu = 0;
-                    if (fit_per_cu == 0) {
-                        int n = 0;
-                        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, pinn_fit_kernel<PINN_INST_HP, ND, N2, MT, LHC, ACTC, COMB, VAR, 1>,
-                                                                         THREADS, smem) != hipSuccess || n < 1) n = -1;
-                        fit_per_cu = n;
-                    }
-                    int dev = 0, cus = 0;
-                    if (fit_per_cu < 1 || hipGetDevice(&dev) != hipSuccess ||
-                        hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || grid > fit_per_cu * cus) return 1;
+                static int fit_per_cu = 0;
+                if (fit_per_cu == 0) {
+                    int n = 0;
+                    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, pinn_fit_kernel<PINN_INST_HP, ND, N2, MT, LHC, ACTC, COMB, VAR, 1>,
+                                                                     THREADS, smem) != hipSuccess || n < 1) n = -1;
+                    fit_per_cu = n;
                 }
-                hipLaunchKernelGGL((pinn_fit_kernel<PINN_INST_HP, ND, N2, MT, LHC, ACTC, COMB, VAR, 1>), dim3(grid), dim3(THREADS), smem,
-                                   (hipStream_t)stream, *a, *fp);
+                int dev = 0, cus = 0;
+                if (fit_per_cu < 1 || hipGetDevice(&dev) != hipSuccess ||
+                    hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || req.grid > fit_per_cu * cus) return 1;
 #endif
                 snprintf(g_pinn_last_kernel_name, sizeof(g_pinn_last_kernel_name), "pinn_fit_kernel<%d,%d,%d,%d,%d,%d,%s,%d,1>",
                          PINN_INST_HP, ND, N2, MT, LHC, ACTC, COMB ? "true" : "false", VAR);
-            } else {
-                if constexpr (FIT_VW >= 2) {
-                    // LDS: the virtual workgroups' blocks + W^T, then what stays resident (state, rows, batch, pre-pass rows)
-                    const long long res_bytes = 4 * (FV::BASE_FLOATS + FV::resident_floats(a->p_core, fp->n, a->d, a->n_aux));
-                    if (res_bytes > 160 * 1024 - 128) return 1;       // (the rest: pinn_fit_kernel's static LDS -- bail flag, update rule)
-#ifdef PINN_EMU
-                    const PinnKArgs args = *a; const PinnFitP fargs = *fp;
-                    emu::launch(1, C::NTHREADS * FIT_VW, (size_t)res_bytes,
-                                [&] { pinn_fit_kernel<PINN_INST_HP, ND, N2, MT, LHC, ACTC, COMB, VAR, FIT_VW>(args, fargs); });
-#else
-                    static unsigned long long fit1_attr_done = 0;
-                    if (pinn_set_smem_attr(reinterpret_cast<const void*>(&pinn_fit_kernel<PINN_INST_HP, ND, N2, MT, LHC, ACTC, COMB, VAR, FIT_VW>),
-                                           160 * 1024 - 128, fit1_attr_done)) return 2;
-                    hipLaunchKernelGGL((pinn_fit_kernel<PINN_INST_HP, ND, N2, MT, LHC, ACTC, COMB, VAR, FIT_VW>), dim3(1),
-                                       dim3(C::NTHREADS * FIT_VW), (size_t)res_bytes, (hipStream_t)stream, *a, *fp);
-#endif
-                    snprintf(g_pinn_last_kernel_name, sizeof(g_pinn_last_kernel_name), "pinn_fit_kernel<%d,%d,%d,%d,%d,%d,%s,%d,%d>",
-                             PINN_INST_HP, ND, N2, MT, LHC, ACTC, COMB ? "true" : "false", VAR, FIT_VW);
-                } else {
-                    return 1;
-                }
+                return pinn_launch_kernel<pinn_fit_kernel<PINN_INST_HP, ND, N2, MT, LHC, ACTC, COMB, VAR, 1>>(req.grid, THREADS, smem, smem, req.stream,
+                                                                                                           *a, *req.fit);
             }
-#ifdef PINN_EMU
-            return 0;
-#else
-            return hipGetLastError() == hipSuccess ? 0 : 2;
-#endif
+            if constexpr (FIT_VW >= 2) {
+                // LDS: the virtual workgroups' blocks + W^T, then what stays resident (state, rows, batch, pre-pass rows)
+                const long long res_bytes = 4 * (FV::BASE_FLOATS + FV::resident_floats(a->p_core, req.fit->n, a->d, a->n_aux));
+                if (res_bytes > 160 * 1024 - 128) return 1;       // (the rest: pinn_fit_kernel's static LDS -- bail flag, update rule)
+                snprintf(g_pinn_last_kernel_name, sizeof(g_pinn_last_kernel_name), "pinn_fit_kernel<%d,%d,%d,%d,%d,%d,%s,%d,%d>",
+                         PINN_INST_HP, ND, N2, MT, LHC, ACTC, COMB ? "true" : "false", VAR, FIT_VW);
+                return pinn_launch_kernel<pinn_fit_kernel<PINN_INST_HP, ND, N2, MT, LHC, ACTC, COMB, VAR, FIT_VW>>(
+                    1, C::NTHREADS * FIT_VW, (size_t)res_bytes, 160 * 1024 - 128, req.stream, *a, *req.fit);
+            }
         }
         return 1;
-    }
 #else
-    if (query == 3) { info[0] = 0; info[1] = 0; info[2] = 0; return 0; }
-    if (query == 2 || query == 4) return 1;
+        if (req.op == PinnLaunchOp::FitProbe) { *req.probe = PinnFitProbe(); return 0; }
+        return 1;
 #endif
-    g_pinn_last_kernel = (VAR & 48) ? 2 : 0;
+    }
+    g_pinn_last_kernel = pinn_var_spec(VAR) ? 2 : 0;
     snprintf(g_pinn_last_kernel_name, sizeof(g_pinn_last_kernel_name), "pinn_tile_kernel<%d,%d,%d,%d,%d,%d,%s,%d>",
              PINN_INST_HP, ND, N2, MT, LHC, ACTC, COMB ? "true" : "false", VAR);
-#ifdef PINN_EMU
-    const PinnKArgs args = *a;
-    emu::launch(grid, THREADS, smem, [&] { pinn_tile_kernel<PINN_INST_HP, ND, N2, MT, LHC, ACTC, COMB, VAR>(args); });
-    return 0;
-#else
-    static unsigned long long attr_done = 0;
-    if (pinn_set_smem_attr(reinterpret_cast<const void*>(&pinn_tile_kernel<PINN_INST_HP, ND, N2, MT, LHC, ACTC, COMB, VAR>),
-                           smem, attr_done)) return 2;
-    hipLaunchKernelGGL((pinn_tile_kernel<PINN_INST_HP, ND, N2, MT, LHC, ACTC, COMB, VAR>), dim3(grid), dim3(THREADS), smem,
-                       (hipStream_t)stream, *a);
-    return hipGetLastError() == hipSuccess ? 0 : 2;
-#endif
+    return pinn_launch_kernel<pinn_tile_kernel<PINN_INST_HP, ND, N2, MT, LHC, ACTC, COMB, VAR>>(req.grid, THREADS, smem, smem, req.stream, *a);
 }
 }  // namespace
 
 #if PINN_INST_HP >= 128
 namespace {
 template <int ND, int N2, bool COMB, int MT, bool SPLIT = false, bool SKIPS = false, bool HEAVY = false, bool ALLACT = false>
-int launch_wgrad(const PinnKArgs* a, int grid, void* stream, int query, long long* info) {
+int launch_wgrad(const PinnKArgs* a, const PinnLaunchReq& req) {
     using W = PinnWgCfg<PINN_INST_HP, ND, N2, MT, SPLIT>;
     constexpr size_t smem = (size_t)W::SMEM_FLOATS * sizeof(float);
-    if (query) {
-        info[0] = (long long)smem;
-        info[1] = W::NTHREADS;
-        info[3] = W::WGS_PER_CU;
+    if (req.op == PinnLaunchOp::Plan) {
+        req.info->smem_bytes = (long long)smem;
+        req.info->threads = W::NTHREADS;
+        req.info->per_cu = W::WGS_PER_CU;
         return 0;
     }
+    if (req.op != PinnLaunchOp::Launch) return 1;
     snprintf(g_pinn_last_wgrad_name, sizeof(g_pinn_last_wgrad_name), "pinn_wgrad_kernel<%d,%d,%d,%s,%d,%s,%s,%s%s>", PINN_INST_HP, ND, N2,
              COMB ? "true" : "false", MT, SPLIT ? "true" : "false", SKIPS ? "true" : "false", HEAVY ? "true" : "false", ALLACT ? ",true" : "");
-#ifdef PINN_EMU
-    const PinnKArgs args = *a;
-    emu::launch(grid, W::NTHREADS, smem, [&] { pinn_wgrad_kernel<PINN_INST_HP, ND, N2, COMB, MT, SPLIT, SKIPS, HEAVY, ALLACT>(args); });
-    return 0;
-#else
-    static unsigned long long attr_done = 0;
-    if (pinn_set_smem_attr(reinterpret_cast<const void*>(&pinn_wgrad_kernel<PINN_INST_HP, ND, N2, COMB, MT, SPLIT, SKIPS, HEAVY, ALLACT>), smem, attr_done)) return 2;
-    hipLaunchKernelGGL((pinn_wgrad_kernel<PINN_INST_HP, ND, N2, COMB, MT, SPLIT, SKIPS, HEAVY, ALLACT>), dim3(grid), dim3(W::NTHREADS), smem,
-                       (hipStream_t)stream, *a);
-    return hipGetLastError() == hipSuccess ? 0 : 2;
-#endif
+    return pinn_launch_kernel<pinn_wgrad_kernel<PINN_INST_HP, ND, N2, COMB, MT, SPLIT, SKIPS, HEAVY, ALLACT>>(req.grid, W::NTHREADS, smem, smem,
+                                                                                                             req.stream, *a);
+}
+
+// the wide shape-specialised kernel (BASELINE configs 3 / 5 and their split-bf16 twins): tanh fixed at compile time where every layer
+// carries it, the one-bit run-time code (Sigmoid nets) otherwise -- PINN_WIDE_TANH_STATIC above
+template <int ND, int VAR>
+int launch_wide_spec(const PinnKArgs* a, const PinnLaunchReq& req) {
+    if (PINN_WIDE_TANH_STATIC && a->act == PINN_ACT_TANH) return launch_one<ND, 1, -1, PINN_ACT_TANH, PINN_WIDE_MT, true, VAR>(a, req);
+    return launch_one<ND, 1, -1, -1, PINN_WIDE_MT, true, VAR>(a, req);
 }
 }  // namespace
 #endif
@@ -245,24 +221,22 @@ int launch_wgrad(const PinnKArgs* a, int grid, void* stream, int query, long lon
 // third / fourth order and the combined second-order stream (S >= 4) do not exist at this width. Generic depth (up to eight hidden
 // layers), streamed weight gradients (pinn_wgrad_kernel in four 256 x 256 block passes); plain Tanh / Sigmoid nets on the plain kernels,
 // activation codes 0 .. 7 and skips on the first set of full breadth kernels; no split-bf16 twins, no second breadth set.
-int pinn_launch_tile_hp512(int nd, int n2, const PinnKArgs* a, int grid, void* stream, int query, long long* info) {
+int pinn_launch_tile_hp512(int nd, int n2, const PinnKArgs* a, const PinnLaunchReq& req) {
     if (a->comb || pinn_n3(n2) || pinn_needs_allact(a)) return 1;
-    bool plain = a->n_skips == 0;
-    for (int i = 0; i <= a->lh; ++i) plain = plain && pinn_act_code(a->act_codes, i) < 2;
+    const bool plain = a->n_skips == 0 && pinn_plain_acts(a);
 #define PINN_T512(ND, N2)                                                                                       \
-    if (nd == ND && n2 == N2) return plain ? launch_one<ND, N2, -1, -1, 1, false, 128>(a, grid, stream, query, info) \
-                                           : launch_one<ND, N2, -1, -1, 1, false, 8 | 128>(a, grid, stream, query, info);
+    if (nd == ND && n2 == N2) return plain ? launch_one<ND, N2, -1, -1, 1, false, PINN_VAR_WGX>(a, req)           \
+                                           : launch_one<ND, N2, -1, -1, 1, false, PINN_VAR_BREADTH | PINN_VAR_WGX>(a, req);
     PINN_T512(0, 0) PINN_T512(1, 0) PINN_T512(1, 1) PINN_T512(2, 0)
 #undef PINN_T512
     return 1;
 }
-int pinn_launch_wgrad_hp512(int nd, int n2, int comb, int mt, const PinnKArgs* a, int grid, void* stream, int query, long long* info) {
+int pinn_launch_wgrad_hp512(int nd, int n2, int comb, int mt, const PinnKArgs* a, const PinnLaunchReq& req) {
     if (comb || mt != 1 || pinn_n3(n2) || pinn_needs_allact(a)) return 1;
-    bool plain = a->n_skips == 0;
-    for (int i = 0; i <= a->lh; ++i) plain = plain && pinn_act_code(a->act_codes, i) < 2;
+    const bool plain = a->n_skips == 0 && pinn_plain_acts(a);
 #define PINN_W512(ND, N2)                                                                                       \
-    if (nd == ND && n2 == N2) return plain ? launch_wgrad<ND, N2, false, 1>(a, grid, stream, query, info)            \
-                                           : launch_wgrad<ND, N2, false, 1, false, true, true>(a, grid, stream, query, info);
+    if (nd == ND && n2 == N2) return plain ? launch_wgrad<ND, N2, false, 1>(a, req)            \
+                                           : launch_wgrad<ND, N2, false, 1, false, true, true>(a, req);
     PINN_W512(0, 0) PINN_W512(1, 0) PINN_W512(1, 1) PINN_W512(2, 0)
 #undef PINN_W512
     return 1;
@@ -279,12 +253,12 @@ int pinn_launch_wgrad_hp512(int nd, int n2, int comb, int mt, const PinnKArgs* a
 #define PINN_SPLIT_MT_CFG4 2
 #endif
 #ifndef PINN_SPLIT_VAR
-#define PINN_SPLIT_VAR 256      // second wave per SIMD of the split kernels: two teams in one workgroup (2 = two workgroups per CU: refused, pinn_kernel.h)
+#define PINN_SPLIT_VAR PINN_VAR_TEAMS2      // second wave per SIMD of the split kernels: two teams in one workgroup (2 = two workgroups per CU: refused, pinn_kernel.h)
 #endif
 #ifndef PINN_CFG2_VAR
 // the Poisson-box kernel of BASELINE configs 1 / 2 at width 64: two teams of 16-point tiles (VAR 256) instead of one wave
 // per SIMD on 32-point tiles
-#define PINN_CFG2_VAR 256
+#define PINN_CFG2_VAR PINN_VAR_TEAMS2
 #endif
 #ifndef PINN_CFG2_MT
 #define PINN_CFG2_MT 1
@@ -300,103 +274,89 @@ int pinn_launch_wgrad_hp512(int nd, int n2, int comb, int mt, const PinnKArgs* a
 // strategy 0.1957 ms against 0.1983 - 0.1997 under iterative-ilp, which BASELINE config 4's kernel in turn needs: 0.2034 against 0.2067)
 #if defined(PINN_INST_OWN)
 #if PINN_INST_HP == 64 && PINN_INST_OWN == 1
-int pinn_launch_cfg2_hp64(const PinnKArgs* a, int grid, void* stream, int query, long long* info) {
-    return launch_one<2, 1, 3, PINN_ACT_TANH, PINN_CFG2_MT, true, PINN_CFG2_VAR | 16 | PINN_CFG2_SLABL>(a, grid, stream, query, info);
+int pinn_launch_cfg2_hp64(const PinnKArgs* a, const PinnLaunchReq& req) {
+    return launch_one<2, 1, 3, PINN_ACT_TANH, PINN_CFG2_MT, true, PINN_CFG2_VAR | PINN_VAR_SPEC(1) | PINN_CFG2_SLABL>(a, req);
 }
 // ... and its twin with a residual PROGRAM (round 6, VAR 2048: non-affine equations / trainable V(...) scalars on the Poisson-box shape --
 // bench.py --workload program; they ran on the general 32-point, one-wave-per-SIMD kernel: 46 % MFMA-busy, profiles/r06_breadth_program_summary.txt)
-int pinn_launch_cfg2_prog_hp64(const PinnKArgs* a, int grid, void* stream, int query, long long* info) {
-    return launch_one<2, 1, 3, PINN_ACT_TANH, 1, true, 256 | 16 | 2048>(a, grid, stream, query, info);
+int pinn_launch_cfg2_prog_hp64(const PinnKArgs* a, const PinnLaunchReq& req) {
+    return launch_one<2, 1, 3, PINN_ACT_TANH, 1, true, PINN_VAR_TEAMS2 | PINN_VAR_SPEC(1) | PINN_VAR_PROGRAM>(a, req);
 }
 // ... and with the 'Sin' activation (static, no skips: the two-way activation switch of the plain kernels is not in play, so the breadth bit
 // VAR 8 is not needed; bench.py --workload sin64 ran on the one-team kernel <..., 8 | 16>: one wave per SIMD, 47 % MFMA-busy)
-int pinn_launch_cfg2_sin_hp64(const PinnKArgs* a, int grid, void* stream, int query, long long* info) {
-    return launch_one<2, 1, 3, PINN_ACT_SIN, 1, true, 256 | 16>(a, grid, stream, query, info);
+int pinn_launch_cfg2_sin_hp64(const PinnKArgs* a, const PinnLaunchReq& req) {
+    return launch_one<2, 1, 3, PINN_ACT_SIN, 1, true, PINN_VAR_TEAMS2 | PINN_VAR_SPEC(1)>(a, req);
 }
 // ... and the evolution-in-a-box shape in (x, t) (PinnShape 2: boundary binding in x, initial condition in t -- heat / wave / Burgers in one space
 // dimension, the tutorial's time-dependent problems on a 4 x 64 Tanh net), affine residual or residual program: S = 4 like the Poisson box, so the
 // two-team form fits; these ran on the general 32-point kernel
-int pinn_launch_evo2_hp64(const PinnKArgs* a, int grid, void* stream, int query, long long* info) {
-    return launch_one<2, 1, 3, PINN_ACT_TANH, 1, true, 256 | 32>(a, grid, stream, query, info);
+int pinn_launch_evo2_hp64(const PinnKArgs* a, const PinnLaunchReq& req) {
+    return launch_one<2, 1, 3, PINN_ACT_TANH, 1, true, PINN_VAR_TEAMS2 | PINN_VAR_SPEC(2)>(a, req);
 }
-int pinn_launch_evo2_prog_hp64(const PinnKArgs* a, int grid, void* stream, int query, long long* info) {
-    return launch_one<2, 1, 3, PINN_ACT_TANH, 1, true, 256 | 32 | 2048>(a, grid, stream, query, info);
+int pinn_launch_evo2_prog_hp64(const PinnKArgs* a, const PinnLaunchReq& req) {
+    return launch_one<2, 1, 3, PINN_ACT_TANH, 1, true, PINN_VAR_TEAMS2 | PINN_VAR_SPEC(2) | PINN_VAR_PROGRAM>(a, req);
 }
 #endif
 #elif defined(PINN_INST_SPLIT)
 #if PINN_INST_HP == 64 && PINN_INST_SPLIT == 1
-int pinn_launch_split_hp64_1(const PinnKArgs* a, int grid, void* stream, int query, long long* info) {
-    return launch_one<2, 1, 3, PINN_ACT_TANH, PINN_SPLIT_MT_CFG2, true, PINN_SPLIT_VAR | 16 | 512>(a, grid, stream, query, info);
+int pinn_launch_split_hp64_1(const PinnKArgs* a, const PinnLaunchReq& req) {
+    return launch_one<2, 1, 3, PINN_ACT_TANH, PINN_SPLIT_MT_CFG2, true, PINN_SPLIT_VAR | PINN_VAR_SPEC(1) | PINN_VAR_SPLIT>(a, req);
 }
 #elif PINN_INST_HP == 64
-int pinn_launch_split_hp64_2(const PinnKArgs* a, int grid, void* stream, int query, long long* info) {
-    return launch_one<1, 0, 3, PINN_ACT_TANH, PINN_SPLIT_MT_CFG4, false, PINN_SPLIT_VAR | 48 | 512>(a, grid, stream, query, info);
+int pinn_launch_split_hp64_2(const PinnKArgs* a, const PinnLaunchReq& req) {
+    return launch_one<1, 0, 3, PINN_ACT_TANH, PINN_SPLIT_MT_CFG4, false, PINN_SPLIT_VAR | PINN_VAR_SPEC(3) | PINN_VAR_SPLIT>(a, req);
 }
 #elif PINN_INST_HP == 128
 // the WGX kernels of BASELINE configs 3 (heat, width 128) and 5 (wave, width 256) with split-bf16 forward / data-gradient GEMMs
-int pinn_launch_split_hp128(const PinnKArgs* a, int grid, void* stream, int query, long long* info) {
-    if (PINN_WIDE_TANH_STATIC && a->act == PINN_ACT_TANH) return launch_one<3, 1, -1, PINN_ACT_TANH, PINN_WIDE_MT, true, 32 | 128 | 512>(a, grid, stream, query, info);
-    return launch_one<3, 1, -1, -1, PINN_WIDE_MT, true, 32 | 128 | 512>(a, grid, stream, query, info);
+int pinn_launch_split_hp128(const PinnKArgs* a, const PinnLaunchReq& req) {
+    return launch_wide_spec<3, PINN_VAR_SPEC(2) | PINN_VAR_WGX | PINN_VAR_SPLIT>(a, req);
 }
 // (the split-bf16 weight-gradient kernel lives here as well: every kernel with bf16 MFMAs in the units build.py takes through asm_guard.py)
-int pinn_launch_wgrad_split_hp128(const PinnKArgs* a, int grid, void* stream, int query, long long* info) {
-    return launch_wgrad<3, 1, true, PINN_WIDE_MT, true>(a, grid, stream, query, info);
+int pinn_launch_wgrad_split_hp128(const PinnKArgs* a, const PinnLaunchReq& req) {
+    return launch_wgrad<3, 1, true, PINN_WIDE_MT, true>(a, req);
 }
 #else
-int pinn_launch_split_hp256(const PinnKArgs* a, int grid, void* stream, int query, long long* info) {
-    if (PINN_WIDE_TANH_STATIC && a->act == PINN_ACT_TANH) return launch_one<2, 1, -1, PINN_ACT_TANH, PINN_WIDE_MT, true, 32 | 128 | 512>(a, grid, stream, query, info);
-    return launch_one<2, 1, -1, -1, PINN_WIDE_MT, true, 32 | 128 | 512>(a, grid, stream, query, info);
+int pinn_launch_split_hp256(const PinnKArgs* a, const PinnLaunchReq& req) {
+    return launch_wide_spec<2, PINN_VAR_SPEC(2) | PINN_VAR_WGX | PINN_VAR_SPLIT>(a, req);
 }
-int pinn_launch_wgrad_split_hp256(const PinnKArgs* a, int grid, void* stream, int query, long long* info) {
-    return launch_wgrad<2, 1, true, PINN_WIDE_MT, true>(a, grid, stream, query, info);
+int pinn_launch_wgrad_split_hp256(const PinnKArgs* a, const PinnLaunchReq& req) {
+    return launch_wgrad<2, 1, true, PINN_WIDE_MT, true>(a, req);
 }
 #endif
 #else      // everything below: the regular per-width translation unit
-int pinn_launch_cfg2_hp64(const PinnKArgs* a, int grid, void* stream, int query, long long* info);
-int pinn_launch_cfg2_prog_hp64(const PinnKArgs* a, int grid, void* stream, int query, long long* info);
-int pinn_launch_cfg2_sin_hp64(const PinnKArgs* a, int grid, void* stream, int query, long long* info);
-int pinn_launch_evo2_hp64(const PinnKArgs* a, int grid, void* stream, int query, long long* info);
-int pinn_launch_evo2_prog_hp64(const PinnKArgs* a, int grid, void* stream, int query, long long* info);
-int pinn_launch_split_hp64_1(const PinnKArgs* a, int grid, void* stream, int query, long long* info);
-int pinn_launch_split_hp64_2(const PinnKArgs* a, int grid, void* stream, int query, long long* info);
-int pinn_launch_split_hp128(const PinnKArgs* a, int grid, void* stream, int query, long long* info);
-int pinn_launch_split_hp256(const PinnKArgs* a, int grid, void* stream, int query, long long* info);
-int pinn_launch_wgrad_split_hp128(const PinnKArgs* a, int grid, void* stream, int query, long long* info);
-int pinn_launch_wgrad_split_hp256(const PinnKArgs* a, int grid, void* stream, int query, long long* info);
+int pinn_launch_cfg2_hp64(const PinnKArgs* a, const PinnLaunchReq& req);
+int pinn_launch_cfg2_prog_hp64(const PinnKArgs* a, const PinnLaunchReq& req);
+int pinn_launch_cfg2_sin_hp64(const PinnKArgs* a, const PinnLaunchReq& req);
+int pinn_launch_evo2_hp64(const PinnKArgs* a, const PinnLaunchReq& req);
+int pinn_launch_evo2_prog_hp64(const PinnKArgs* a, const PinnLaunchReq& req);
+int pinn_launch_split_hp64_1(const PinnKArgs* a, const PinnLaunchReq& req);
+int pinn_launch_split_hp64_2(const PinnKArgs* a, const PinnLaunchReq& req);
+int pinn_launch_split_hp128(const PinnKArgs* a, const PinnLaunchReq& req);
+int pinn_launch_split_hp256(const PinnKArgs* a, const PinnLaunchReq& req);
+int pinn_launch_wgrad_split_hp128(const PinnKArgs* a, const PinnLaunchReq& req);
+int pinn_launch_wgrad_split_hp256(const PinnKArgs* a, const PinnLaunchReq& req);
 
 #if PINN_INST_HP == 64 && PINN_CHAIN
 namespace {
-// pinn_chain_kernel: to the host a workgroup of four "teams" (info[10]: the chain / wgrad wave pairs) on tiles of 16 * MT points
+// pinn_chain_kernel: to the host a workgroup of four "teams" (PinnLaunchInfo::teams: the chain / wgrad wave pairs) on tiles of 16 * MT points
 template <int ND, int N2, int LHC, int MT, bool COMB, int SPEC>
-int launch_chain(const PinnKArgs* a, int grid, void* stream, int query, long long* info) {
+int launch_chain(const PinnKArgs* a, const PinnLaunchReq& req) {
     using C = PinnChainCfg<ND, N2, MT, LHC>;
     constexpr size_t smem = (size_t)C::SMEM_FLOATS * sizeof(float);
     static_assert(smem <= 160 * 1024, "LDS carve of the chain kernel");
-    if (query) {
-        info[0] = (long long)smem;
-        info[1] = C::NTHREADS;
-        info[2] = (long long)C::SLAB_VEC4 * C::NP;
-        info[3] = 1;
-        info[4] = MT;
-        info[5] = 0; info[6] = 0; info[7] = 0;
-        info[8] = COMB ? 1 : 0;
-        info[9] = 0;
-        info[10] = C::NP;
+    if (req.op == PinnLaunchOp::Plan) {
+        req.info->smem_bytes = (long long)smem;
+        req.info->threads = C::NTHREADS;
+        req.info->slab_vec4_per_wg = (long long)C::SLAB_VEC4 * C::NP;
+        req.info->mt = MT;
+        req.info->teams = C::NP;
         return 0;
     }
+    if (req.op != PinnLaunchOp::Launch) return 1;
     g_pinn_last_kernel = 2;
     snprintf(g_pinn_last_kernel_name, sizeof(g_pinn_last_kernel_name), "pinn_chain_kernel<%d,%d,%d,%d,%s,%d>",
              ND, N2, MT, LHC, COMB ? "true" : "false", SPEC);
-#ifdef PINN_EMU
-    const PinnKArgs args = *a;
-    emu::launch(grid, C::NTHREADS, smem, [&] { pinn_chain_kernel<ND, N2, MT, LHC, COMB, SPEC>(args); });
-    return 0;
-#else
-    static unsigned long long attr_done = 0;
-    if (pinn_set_smem_attr(reinterpret_cast<const void*>(&pinn_chain_kernel<ND, N2, MT, LHC, COMB, SPEC>), smem, attr_done)) return 2;
-    hipLaunchKernelGGL((pinn_chain_kernel<ND, N2, MT, LHC, COMB, SPEC>), dim3(grid), dim3(C::NTHREADS), smem, (hipStream_t)stream, *a);
-    return hipGetLastError() == hipSuccess ? 0 : 2;
-#endif
+    return pinn_launch_kernel<pinn_chain_kernel<ND, N2, MT, LHC, COMB, SPEC>>(req.grid, C::NTHREADS, smem, smem, req.stream, *a);
 }
 }  // namespace
 #ifndef PINN_CHAIN_MT_CFG2
@@ -412,8 +372,7 @@ int launch_chain(const PinnKArgs* a, int grid, void* stream, int query, long lon
 // skips carry activation outputs; the four commonest stream shapes), 2 = full breadth (VAR 8). Shared by the tile and the
 // weight-gradient launcher of the widths whose kernels come in pairs.
 static int pinn_breadth_kind(const PinnKArgs* a, int nd, int n2) {
-    bool plain_acts = true;
-    for (int i = 0; i <= a->lh; ++i) plain_acts = plain_acts && pinn_act_code(a->act_codes, i) < 2;
+    const bool plain_acts = pinn_plain_acts(a);
     if (a->n_skips == 0 && plain_acts) return 0;
     if (plain_acts && !a->skip_src_pre && !a->skip_outer) {        // (nested skips: the full breadth kernels park the outer skip's jets)
         if (a->comb) { if (n2 == 1 && (nd == 2 || nd == 3)) return 1; }
@@ -424,25 +383,24 @@ static int pinn_breadth_kind(const PinnKArgs* a, int nd, int n2) {
 
 #ifndef PINN_INST_ALLACT
 // streamed weight-gradient kernel matching the WGX tile kernel of (nd, n2, comb, mt): same jet structure, same lane-private layout
-int PINN_CAT(pinn_launch_wgrad_hp, PINN_INST_HP)(int nd, int n2, int comb, int mt, const PinnKArgs* a, int grid, void* stream,
-                                                  int query, long long* info) {
+int PINN_CAT(pinn_launch_wgrad_hp, PINN_INST_HP)(int nd, int n2, int comb, int mt, const PinnKArgs* a, const PinnLaunchReq& req) {
     if (mt != PINN_WIDE_MT && mt != 1) return 1;
     const int kind = pinn_breadth_kind(a, nd, n2);
     if (kind == 1) {
         // partners of the VAR 8 | 1024 | 128 tile kernels below (skips over Tanh / Sigmoid layers)
         if (mt != 1) return 1;
-        if (comb && n2 == 1 && nd == 2) return launch_wgrad<2, 1, true, 1, false, true>(a, grid, stream, query, info);
-        if (comb && n2 == 1 && nd == 3) return launch_wgrad<3, 1, true, 1, false, true>(a, grid, stream, query, info);
-        if (!comb && nd == 1 && n2 == 1) return launch_wgrad<1, 1, false, 1, false, true>(a, grid, stream, query, info);
-        if (!comb && nd == 2 && n2 == 2) return launch_wgrad<2, 2, false, 1, false, true>(a, grid, stream, query, info);
+        if (comb && n2 == 1 && nd == 2) return launch_wgrad<2, 1, true, 1, false, true>(a, req);
+        if (comb && n2 == 1 && nd == 3) return launch_wgrad<3, 1, true, 1, false, true>(a, req);
+        if (!comb && nd == 1 && n2 == 1) return launch_wgrad<1, 1, false, 1, false, true>(a, req);
+        if (!comb && nd == 2 && n2 == 2) return launch_wgrad<2, 2, false, 1, false, true>(a, req);
         return 1;
     }
     if (kind == 2) {
         // ... of the full breadth kernels (VAR 8 | 128): any activation, any skip form
         if (mt != 1) return 1;
 #define PINN_WG_HEAVY(ND, N2, COMB) \
-        if (nd == ND && n2 == N2 && (comb != 0) == COMB) return pinn_needs_allact(a) ? PINN_CAT(pinn_launch_wgrad2_hp, PINN_INST_HP)(nd, n2, comb, a, grid, stream, query, info) \
-                                                                                     : launch_wgrad<ND, N2, COMB, 1, false, true, true>(a, grid, stream, query, info);
+        if (nd == ND && n2 == N2 && (comb != 0) == COMB) return pinn_needs_allact(a) ? PINN_CAT(pinn_launch_wgrad2_hp, PINN_INST_HP)(nd, n2, comb, a, req) \
+                                                                                     : launch_wgrad<ND, N2, COMB, 1, false, true, true>(a, req);
 #ifndef PINN_ONLY_BASELINE
         PINN_WG_HEAVY(0, 0, false) PINN_WG_HEAVY(1, 0, false) PINN_WG_HEAVY(1, 1, false) PINN_WG_HEAVY(2, 0, false)
         PINN_WG_HEAVY(2, 2, false) PINN_WG_HEAVY(3, 2, false) PINN_WG_HEAVY(2, 1, true) PINN_WG_HEAVY(3, 1, true)
@@ -458,24 +416,24 @@ int PINN_CAT(pinn_launch_wgrad_hp, PINN_INST_HP)(int nd, int n2, int comb, int m
     // pairs with the exact-fp32 tile kernel as well
 #if PINN_INST_HP == 128
     if (a->gemm_mode == PINN_GEMM_BF16X3 && nd == 3 && n2 == 1 && comb && mt == PINN_WIDE_MT)
-        return pinn_launch_wgrad_split_hp128(a, grid, stream, query, info);
+        return pinn_launch_wgrad_split_hp128(a, req);
 #else
     if (a->gemm_mode == PINN_GEMM_BF16X3 && nd == 2 && n2 == 1 && comb && mt == PINN_WIDE_MT)
-        return pinn_launch_wgrad_split_hp256(a, grid, stream, query, info);
+        return pinn_launch_wgrad_split_hp256(a, req);
 #endif
 #define PINN_WG_CASE(ND, N2, COMB)                                                                                  \
     if (nd == ND && n2 == N2 && (comb != 0) == COMB) {                                                              \
-        if (mt == 1) return launch_wgrad<ND, N2, COMB, 1>(a, grid, stream, query, info);                            \
-        return launch_wgrad<ND, N2, COMB, PINN_WIDE_MT>(a, grid, stream, query, info);                             \
+        if (mt == 1) return launch_wgrad<ND, N2, COMB, 1>(a, req);                            \
+        return launch_wgrad<ND, N2, COMB, PINN_WIDE_MT>(a, req);                             \
     }
 #ifdef PINN_ONLY_BASELINE
     // experiment builds: only the BASELINE kernels; sizing queries of any other shape get their answer
 #if PINN_INST_HP == 128
     PINN_WG_CASE(3, 1, true)
-    if (query) return launch_wgrad<3, 1, true, PINN_WIDE_MT>(a, grid, stream, query, info);
+    if (req.op == PinnLaunchOp::Plan) return launch_wgrad<3, 1, true, PINN_WIDE_MT>(a, req);
 #else
     PINN_WG_CASE(2, 1, true)
-    if (query) return launch_wgrad<2, 1, true, PINN_WIDE_MT>(a, grid, stream, query, info);
+    if (req.op == PinnLaunchOp::Plan) return launch_wgrad<2, 1, true, PINN_WIDE_MT>(a, req);
 #endif
 #else
     PINN_WG_CASE(0, 0, false) PINN_WG_CASE(1, 0, false) PINN_WG_CASE(1, 1, false) PINN_WG_CASE(2, 0, false)
@@ -509,7 +467,7 @@ int PINN_CAT(pinn_launch_wgrad_hp, PINN_INST_HP)(int nd, int n2, int comb, int m
 // VAR of the ODE-family kernel of BASELINE config 4: PinnShape 3 (48) | two workgroups per CU (2). With S = 2 streams and
 // 32-point tiles the kernel fits 256 registers, and a second wave per SIMD fills the latency of the vector phases (30 % of
 // this kernel): 0.226 -> 0.203 ms per 131 072 points in a same-box A/B (one wave at 48-point tiles before)
-#define PINN_FAST_VAR_S2 (48 | 256)
+#define PINN_FAST_VAR_S2 (PINN_VAR_SPEC(3) | PINN_VAR_TEAMS2)
 #endif
 #ifndef PINN_CFG4_MT
 #define PINN_CFG4_MT 2
@@ -539,7 +497,7 @@ int PINN_CAT(pinn_launch_wgrad_hp, PINN_INST_HP)(int nd, int n2, int comb, int m
 #endif
 
 // VAR bit of the widths whose hidden->hidden weight gradients come from pinn_wgrad_kernel
-constexpr int WGXV = (PINN_INST_HP >= PINN_WGX_MIN_HP && PINN_INST_HP >= 128) ? 128 : 0;
+constexpr int WGXV = (PINN_INST_HP >= PINN_WGX_MIN_HP && PINN_INST_HP >= 128) ? PINN_VAR_WGX : 0;
 #ifndef PINN_HEAVY_WGX
 #define PINN_HEAVY_WGX 1        // ... of the full breadth kernels (VAR 8) too (round 4; 0: read-modify-write rows of the partial buffer, the A/B partner)
 #endif
@@ -572,9 +530,9 @@ static int pinn_spec_of(const PinnKArgs* a, int nd, int n2, bool program = false
 // (PINN_INST_ALLACT=1) and their weight-gradient partners (=2, widths >= 128) compile as separate units.
 #define PINN_ALLACT_SHAPES(X) X(0, 0, false) X(1, 0, false) X(1, 1, false) X(2, 0, false) X(2, 2, false) X(2, 1, true) X(3, 1, true) X(1, 9, false) X(1, 73, false)
 #if PINN_INST_ALLACT == 1
-int PINN_CAT(pinn_launch_breadth2_hp, PINN_INST_HP)(int nd, int n2, int comb, const PinnKArgs* a, int grid, void* stream, int query, long long* info) {
+int PINN_CAT(pinn_launch_breadth2_hp, PINN_INST_HP)(int nd, int n2, int comb, const PinnKArgs* a, const PinnLaunchReq& req) {
 #ifndef PINN_ONLY_BASELINE
-#define PINN_B2(ND, N2, COMB) if (nd == ND && n2 == N2 && (comb != 0) == COMB) return launch_one<ND, N2, -1, -2, 1, COMB, 8 | WGXH>(a, grid, stream, query, info);
+#define PINN_B2(ND, N2, COMB) if (nd == ND && n2 == N2 && (comb != 0) == COMB) return launch_one<ND, N2, -1, -2, 1, COMB, PINN_VAR_BREADTH | WGXH>(a, req);
     PINN_ALLACT_SHAPES(PINN_B2)
 #undef PINN_B2
 #endif
@@ -582,9 +540,9 @@ int PINN_CAT(pinn_launch_breadth2_hp, PINN_INST_HP)(int nd, int n2, int comb, co
 }
 #endif
 #if PINN_INST_ALLACT == 2 || (PINN_INST_ALLACT == 1 && PINN_INST_HP < 128)
-int PINN_CAT(pinn_launch_wgrad2_hp, PINN_INST_HP)(int nd, int n2, int comb, const PinnKArgs* a, int grid, void* stream, int query, long long* info) {
+int PINN_CAT(pinn_launch_wgrad2_hp, PINN_INST_HP)(int nd, int n2, int comb, const PinnKArgs* a, const PinnLaunchReq& req) {
 #if PINN_INST_HP >= 128 && !defined(PINN_ONLY_BASELINE)
-#define PINN_W2(ND, N2, COMB) if (nd == ND && n2 == N2 && (comb != 0) == COMB) return launch_wgrad<ND, N2, COMB, 1, false, true, true, true>(a, grid, stream, query, info);
+#define PINN_W2(ND, N2, COMB) if (nd == ND && n2 == N2 && (comb != 0) == COMB) return launch_wgrad<ND, N2, COMB, 1, false, true, true, true>(a, req);
     PINN_ALLACT_SHAPES(PINN_W2)
 #undef PINN_W2
 #endif
@@ -595,13 +553,13 @@ int PINN_CAT(pinn_launch_wgrad2_hp, PINN_INST_HP)(int nd, int n2, int comb, cons
 #ifndef PINN_INST_ALLACT
 // the full breadth tile kernel of a stream shape: first set (ACTC -1: activation codes 0 .. 7, no nested skips) or second (ACTC -2: all)
 // (the second set lives in a translation unit of its own, -DPINN_INST_ALLACT=1: build.py compiles the units in parallel)
-#define PINN_BREADTH(ND, N2, COMB) (pinn_needs_allact(a) ? PINN_CAT(pinn_launch_breadth2_hp, PINN_INST_HP)(nd, n2, COMB ? 1 : 0, a, grid, stream, query, info) \
-                                                         : launch_one<ND, N2, -1, -1, 1, COMB, 8 | WGXH>(a, grid, stream, query, info))
-int PINN_CAT(pinn_launch_tile_hp, PINN_INST_HP)(int nd, int n2, const PinnKArgs* a, int grid, void* stream,
-                                                 int query, long long* info) {
+#define PINN_BREADTH(ND, N2, COMB) (pinn_needs_allact(a) ? PINN_CAT(pinn_launch_breadth2_hp, PINN_INST_HP)(nd, n2, COMB ? 1 : 0, a, req) \
+                                                         : launch_one<ND, N2, -1, -1, 1, COMB, PINN_VAR_BREADTH | WGXH>(a, req))
+int PINN_CAT(pinn_launch_tile_hp, PINN_INST_HP)(int nd, int n2, const PinnKArgs* a, const PinnLaunchReq& req) {
+    [[maybe_unused]] const bool sizing = req.op == PinnLaunchOp::Plan;
 #define PINN_TRY_FAST(ND, N2, LH, ACT, MT)                                                                             \
     if (nd == ND && n2 == N2 && a->lh == LH && a->act == ACT && !skips)                                                \
-        return launch_one<ND, N2, LH, ACT, MT>(a, grid, stream, query, info);
+        return launch_one<ND, N2, LH, ACT, MT>(a, req);
     // nets with skip connections ('R ... +') or activations other than tanh / sigmoid take the generic-depth kernels
     // compiled with the breadth bit (VAR 8)
 #ifdef PINN_ONLY_BASELINE
@@ -610,38 +568,35 @@ int PINN_CAT(pinn_launch_tile_hp, PINN_INST_HP)(int nd, int n2, const PinnKArgs*
 #if PINN_INST_HP == 64
 #if PINN_CHAIN
     if (a->comb && nd == 2 && n2 == 1 && a->lh == 3 && a->act == PINN_ACT_TANH && pinn_spec_of(a, nd, n2) == 1)
-        return launch_chain<2, 1, 3, PINN_CHAIN_MT_CFG2, true, 1>(a, grid, stream, query, info);
+        return launch_chain<2, 1, 3, PINN_CHAIN_MT_CFG2, true, 1>(a, req);
     if (!a->comb && nd == 1 && n2 == 0 && a->lh == 3 && a->act == PINN_ACT_TANH && pinn_spec_of(a, nd, n2) == 3)
-        return launch_chain<1, 0, 3, PINN_CHAIN_MT_CFG4, false, 3>(a, grid, stream, query, info);
+        return launch_chain<1, 0, 3, PINN_CHAIN_MT_CFG4, false, 3>(a, req);
 #endif
     if (a->gemm_mode == PINN_GEMM_BF16X3) {
         if (a->comb && nd == 2 && n2 == 1 && a->lh == 3 && a->act == PINN_ACT_TANH && pinn_spec_of(a, nd, n2) == 1)
-            return pinn_launch_split_hp64_1(a, grid, stream, query, info);
+            return pinn_launch_split_hp64_1(a, req);
         if (!a->comb && nd == 1 && n2 == 0 && a->lh == 3 && a->act == PINN_ACT_TANH && pinn_spec_of(a, nd, n2) == 3)
-            return pinn_launch_split_hp64_2(a, grid, stream, query, info);
+            return pinn_launch_split_hp64_2(a, req);
     }
-    if (a->comb && nd == 2 && n2 == 1 && (query || (a->lh == 3 && a->act == PINN_ACT_TANH && pinn_spec_of(a, nd, n2) == 1)))
-        return launch_one<2, 1, 3, PINN_ACT_TANH, PINN_CFG2_MT, true, PINN_CFG2_VAR | 16 | PINN_CFG2_SLABL>(a, grid, stream, query, info);
-    if (!a->comb && nd == 1 && n2 == 0 && (query || (a->lh == 3 && a->act == PINN_ACT_TANH && pinn_spec_of(a, nd, n2) == 3)))
-        return launch_one<1, 0, 3, PINN_ACT_TANH, PINN_CFG4_MT, false, PINN_FAST_VAR_S2>(a, grid, stream, query, info);
-    if (query) return launch_one<2, 1, 3, PINN_ACT_TANH, PINN_CFG2_MT, true, PINN_CFG2_VAR | 16 | PINN_CFG2_SLABL>(a, grid, stream, query, info);
+    if (a->comb && nd == 2 && n2 == 1 && (sizing || (a->lh == 3 && a->act == PINN_ACT_TANH && pinn_spec_of(a, nd, n2) == 1)))
+        return launch_one<2, 1, 3, PINN_ACT_TANH, PINN_CFG2_MT, true, PINN_CFG2_VAR | PINN_VAR_SPEC(1) | PINN_CFG2_SLABL>(a, req);
+    if (!a->comb && nd == 1 && n2 == 0 && (sizing || (a->lh == 3 && a->act == PINN_ACT_TANH && pinn_spec_of(a, nd, n2) == 3)))
+        return launch_one<1, 0, 3, PINN_ACT_TANH, PINN_CFG4_MT, false, PINN_FAST_VAR_S2>(a, req);
+    if (sizing) return launch_one<2, 1, 3, PINN_ACT_TANH, PINN_CFG2_MT, true, PINN_CFG2_VAR | PINN_VAR_SPEC(1) | PINN_CFG2_SLABL>(a, req);
 #elif PINN_INST_HP == 128
     if (a->gemm_mode == PINN_GEMM_BF16X3 && WGXV && a->comb && nd == 3 && n2 == 1 && pinn_spec_of(a, nd, n2) == 2)
-        return pinn_launch_split_hp128(a, grid, stream, query, info);
-    if (query || (a->comb && nd == 3 && n2 == 1 && pinn_spec_of(a, nd, n2) == 2))
-        return (PINN_WIDE_TANH_STATIC && a->act == PINN_ACT_TANH) ? launch_one<3, 1, -1, PINN_ACT_TANH, PINN_WIDE_MT, true, 32 | WGXV>(a, grid, stream, query, info)
-                                                               : launch_one<3, 1, -1, -1, PINN_WIDE_MT, true, 32 | WGXV>(a, grid, stream, query, info);
+        return pinn_launch_split_hp128(a, req);
+    if (sizing || (a->comb && nd == 3 && n2 == 1 && pinn_spec_of(a, nd, n2) == 2))
+        return launch_wide_spec<3, PINN_VAR_SPEC(2) | WGXV>(a, req);
 #elif PINN_INST_HP == 256
     if (a->gemm_mode == PINN_GEMM_BF16X3 && WGXV && a->comb && nd == 2 && n2 == 1 && pinn_spec_of(a, nd, n2) == 2)
-        return pinn_launch_split_hp256(a, grid, stream, query, info);
-    if (query || (a->comb && nd == 2 && n2 == 1 && pinn_spec_of(a, nd, n2) == 2))
-        return (PINN_WIDE_TANH_STATIC && a->act == PINN_ACT_TANH) ? launch_one<2, 1, -1, PINN_ACT_TANH, PINN_WIDE_MT, true, 32 | WGXV>(a, grid, stream, query, info)
-                                                               : launch_one<2, 1, -1, -1, PINN_WIDE_MT, true, 32 | WGXV>(a, grid, stream, query, info);
+        return pinn_launch_split_hp256(a, req);
+    if (sizing || (a->comb && nd == 2 && n2 == 1 && pinn_spec_of(a, nd, n2) == 2))
+        return launch_wide_spec<2, PINN_VAR_SPEC(2) | WGXV>(a, req);
 #endif
     return 1;
 #else
-    bool skips = a->n_skips > 0, plain_acts = true;
-    for (int i = 0; i <= a->lh; ++i) plain_acts = plain_acts && pinn_act_code(a->act_codes, i) < 2;     // tanh / sigmoid only
+    bool skips = a->n_skips > 0, plain_acts = pinn_plain_acts(a);
     skips = skips || !plain_acts;
     if (a->skip_src_pre || a->skip_outer) plain_acts = false;   // (the lighter skip kernels, VAR 8 | 1024, carry activation outputs only, one skip at a time)
     const int spec = skips ? 0 : pinn_spec_of(a, nd, n2);
@@ -657,10 +612,10 @@ int PINN_CAT(pinn_launch_tile_hp, PINN_INST_HP)(int nd, int n2, const PinnKArgs*
 #define PINN_SIN_TEAMS 1        // 1: the Dirichlet-box 'Sin' kernel as two teams of 16-point tiles (round 6), 0: one team (round 3's form)
 #endif
                 if (pinn_spec_of(a, nd, n2) == 1 && PINN_SIN_TEAMS && PINN_SIN_MT == 1)
-                    return pinn_launch_cfg2_sin_hp64(a, grid, stream, query, info);
+                    return pinn_launch_cfg2_sin_hp64(a, req);
                 if (pinn_spec_of(a, nd, n2) == 1)       // Dirichlet box, affine residual: the shape facts fixed as for BASELINE config 2
-                    return launch_one<2, 1, 3, PINN_ACT_SIN, PINN_SIN_MT, true, 8 | 16>(a, grid, stream, query, info);
-                return launch_one<2, 1, 3, PINN_ACT_SIN, PINN_SIN_MT, true, 8>(a, grid, stream, query, info);
+                    return launch_one<2, 1, 3, PINN_ACT_SIN, PINN_SIN_MT, true, PINN_VAR_BREADTH | PINN_VAR_SPEC(1)>(a, req);
+                return launch_one<2, 1, 3, PINN_ACT_SIN, PINN_SIN_MT, true, PINN_VAR_BREADTH>(a, req);
             }
 #endif
             // (skips over Tanh / Sigmoid layers only: the breadth kernel without the heavy activation paths, VAR 8 | 1024)
@@ -672,16 +627,16 @@ int PINN_CAT(pinn_launch_tile_hp, PINN_INST_HP)(int nd, int n2, const PinnKArgs*
             // (round 6: bench.py `sin128` sat at 0.49 of the peak executed with 3.8 non-MFMA vector instructions per MFMA -- the run-time activation
             //  switch of the full breadth kernel around `sincos`; its weight-gradient partner stays the HEAVY one, which reads the same slab)
             if (PINN_WIDE_SIN_STATIC && nd == 2 && a->act == PINN_ACT_SIN && a->n_skips == 0 && pinn_spec_of(a, nd, n2) == 1)
-                return launch_one<2, 1, -1, PINN_ACT_SIN, 1, true, 16 | WGXV>(a, grid, stream, query, info);
+                return launch_one<2, 1, -1, PINN_ACT_SIN, 1, true, PINN_VAR_SPEC(1) | WGXV>(a, req);
             // (Dirichlet box, affine residual: the shape facts fixed as for BASELINE config 2 -- the residual nets one meets first)
             // (round 6: Tanh throughout -- the usual residual PINN, bench.py skip128 / skip256: the activation as a compile-time fact here as well)
             if (PINN_WIDE_TANH_STATIC && nd == 2 && a->act == PINN_ACT_TANH && a->n_skips > 0 && !a->skip_src_pre && !a->skip_outer && pinn_spec_of(a, nd, n2) == 1)
-                return launch_one<2, 1, -1, PINN_ACT_TANH, 1, true, 8 | 16 | 1024 | WGXV>(a, grid, stream, query, info);
+                return launch_one<2, 1, -1, PINN_ACT_TANH, 1, true, PINN_VAR_BREADTH | PINN_VAR_SPEC(1) | PINN_VAR_SKIPS_LIGHT | WGXV>(a, req);
             if (nd == 2 && plain_acts && a->n_skips > 0 && pinn_spec_of(a, nd, n2) == 1)
-                return launch_one<2, 1, -1, -1, 1, true, 8 | 16 | 1024 | WGXV>(a, grid, stream, query, info);
+                return launch_one<2, 1, -1, -1, 1, true, PINN_VAR_BREADTH | PINN_VAR_SPEC(1) | PINN_VAR_SKIPS_LIGHT | WGXV>(a, req);
 #endif
-            if (nd == 2 && plain_acts) return launch_one<2, 1, -1, -1, 1, true, 8 | 1024 | WGXV>(a, grid, stream, query, info);
-            if (nd == 3 && plain_acts) return launch_one<3, 1, -1, -1, 1, true, 8 | 1024 | WGXV>(a, grid, stream, query, info);
+            if (nd == 2 && plain_acts) return launch_one<2, 1, -1, -1, 1, true, PINN_VAR_BREADTH | PINN_VAR_SKIPS_LIGHT | WGXV>(a, req);
+            if (nd == 3 && plain_acts) return launch_one<3, 1, -1, -1, 1, true, PINN_VAR_BREADTH | PINN_VAR_SKIPS_LIGHT | WGXV>(a, req);
 #if PINN_INST_HP >= 128
 #ifndef PINN_WIDE_GELU_STATIC
 #define PINN_WIDE_GELU_STATIC 1 // GELU nets (any skip form of the first breadth set) of the streamed widths: the full breadth kernel with the activation fixed at compile time
@@ -689,7 +644,7 @@ int PINN_CAT(pinn_launch_tile_hp, PINN_INST_HP)(int nd, int n2, const PinnKArgs*
             // (round 6: bench.py `gelu256` -- Burgers on a GELU pre-activation ResNet -- ran the full breadth kernel with 299 spilled registers at width 256: every
             //  activation's derivative code competes for them; the skip machinery stays, VAR 8, only the activation is a compile-time fact)
             if (PINN_WIDE_GELU_STATIC && nd == 2 && a->act == PINN_ACT_GELU && WGXH && !pinn_needs_allact(a))
-                return launch_one<2, 1, -1, PINN_ACT_GELU, 1, true, 8 | WGXH>(a, grid, stream, query, info);
+                return launch_one<2, 1, -1, PINN_ACT_GELU, 1, true, PINN_VAR_BREADTH | WGXH>(a, req);
 #endif
             if (nd == 2) return PINN_BREADTH(2, 1, true);
             if (nd == 3) return PINN_BREADTH(3, 1, true);
@@ -698,67 +653,65 @@ int PINN_CAT(pinn_launch_tile_hp, PINN_INST_HP)(int nd, int n2, const PinnKArgs*
         }
 #if PINN_INST_HP == 64
         // the Poisson-type shape of BASELINE configs 1/2 with everything the point stage branches on fixed (VAR 16)
-        if (query && nd == 2 && a->lh == 3 && a->act == PINN_ACT_TANH && PINN_CFG2_SLABL) {
+        if (sizing && nd == 2 && a->lh == 3 && a->act == PINN_ACT_TANH && PINN_CFG2_SLABL) {
             // sizing queries do not know the shape yet: the general kernel's answer (it needs the global slab) plus the
             // W^T scratch the slab-in-LDS kernel would need
-            const int rc = launch_one<2, 1, 3, PINN_ACT_TANH, PINN_FAST_MT_COMB, true, PINN_FAST_VAR_COMB>(a, grid, stream, query, info);
-            info[5] = 3LL * PINN_INST_HP * PINN_INST_HP;
+            const int rc = launch_one<2, 1, 3, PINN_ACT_TANH, PINN_FAST_MT_COMB, true, PINN_FAST_VAR_COMB>(a, req);
+            req.info->wt_floats_per_wg = 3LL * PINN_INST_HP * PINN_INST_HP;
             return rc;
         }
 #if PINN_CHAIN
         if (nd == 2 && a->lh == 3 && a->act == PINN_ACT_TANH && spec == 1)
-            return launch_chain<2, 1, 3, PINN_CHAIN_MT_CFG2, true, 1>(a, grid, stream, query, info);
+            return launch_chain<2, 1, 3, PINN_CHAIN_MT_CFG2, true, 1>(a, req);
 #endif
         // a residual program on the Poisson-box shape: the two-team kernel's twin (exact-fp32 GEMMs in either GEMM mode)
         if (!skips && nd == 2 && a->lh == 3 && a->act == PINN_ACT_TANH && pinn_spec_of(a, nd, n2, true) == 1)
-            return pinn_launch_cfg2_prog_hp64(a, grid, stream, query, info);
+            return pinn_launch_cfg2_prog_hp64(a, req);
 #ifndef PINN_EVO2_TEAMS
 #define PINN_EVO2_TEAMS 1       // 1: the (x, t) evolution shape on two-team kernels (round 6), 0: the general 32-point kernel (before)
 #endif
         if (PINN_EVO2_TEAMS && !skips && nd == 2 && a->lh == 3 && a->act == PINN_ACT_TANH && spec == 2)
-            return pinn_launch_evo2_hp64(a, grid, stream, query, info);
+            return pinn_launch_evo2_hp64(a, req);
         if (PINN_EVO2_TEAMS && !skips && nd == 2 && a->lh == 3 && a->act == PINN_ACT_TANH && pinn_spec_of(a, nd, n2, true) == 2)
-            return pinn_launch_evo2_prog_hp64(a, grid, stream, query, info);
+            return pinn_launch_evo2_prog_hp64(a, req);
         if (nd == 2 && a->lh == 3 && a->act == PINN_ACT_TANH && spec == 1 && a->gemm_mode == PINN_GEMM_BF16X3)
-            return pinn_launch_split_hp64_1(a, grid, stream, query, info);
+            return pinn_launch_split_hp64_1(a, req);
         // (pinn_set_tanh_mode(PINN_TANH_ACCURATE): the same kernel with the polynomial tanh below 0.45 -- ACTC carries PINN_ACT_TANH_POLYBIT)
         if (nd == 2 && a->lh == 3 && a->act == PINN_ACT_TANH && spec == 1 && a->tanh_mode == PINN_TANH_ACCURATE)
-            return launch_one<2, 1, 3, PINN_ACT_TANH | PINN_ACT_TANH_POLYBIT, PINN_CFG2_MT, true, PINN_CFG2_VAR | 16 | PINN_CFG2_SLABL>(a, grid, stream, query, info);
+            return launch_one<2, 1, 3, PINN_ACT_TANH | PINN_ACT_TANH_POLYBIT, PINN_CFG2_MT, true, PINN_CFG2_VAR | PINN_VAR_SPEC(1) | PINN_CFG2_SLABL>(a, req);
         if (nd == 2 && a->lh == 3 && a->act == PINN_ACT_TANH && spec == 1)
-            return pinn_launch_cfg2_hp64(a, grid, stream, query, info);        // (its own translation unit: above)
+            return pinn_launch_cfg2_hp64(a, req);        // (its own translation unit: above)
 #elif PINN_INST_HP == 16
         if (nd == 2 && a->lh == 2 && a->act == PINN_ACT_TANH && spec == 1)
-            return launch_one<2, 1, 2, PINN_ACT_TANH, 1, true, 16>(a, grid, stream, query, info);
+            return launch_one<2, 1, 2, PINN_ACT_TANH, 1, true, PINN_VAR_SPEC(1)>(a, req);
 #elif PINN_INST_HP == 128
         // heat-type shape of BASELINE config 3 on the generic-depth kernel
-        if (nd == 3 && spec == 2 && a->gemm_mode == PINN_GEMM_BF16X3 && WGXV) return pinn_launch_split_hp128(a, grid, stream, query, info);
-        if (nd == 3 && spec == 2) return (PINN_WIDE_TANH_STATIC && a->act == PINN_ACT_TANH) ? launch_one<3, 1, -1, PINN_ACT_TANH, PINN_WIDE_MT, true, 32 | WGXV>(a, grid, stream, query, info)
-                                                               : launch_one<3, 1, -1, -1, PINN_WIDE_MT, true, 32 | WGXV>(a, grid, stream, query, info);
+        if (nd == 3 && spec == 2 && a->gemm_mode == PINN_GEMM_BF16X3 && WGXV) return pinn_launch_split_hp128(a, req);
+        if (nd == 3 && spec == 2) return launch_wide_spec<3, PINN_VAR_SPEC(2) | WGXV>(a, req);
 #elif PINN_INST_HP == 256
         // wave-type shape of BASELINE config 5
-        if (nd == 2 && spec == 2 && a->gemm_mode == PINN_GEMM_BF16X3 && WGXV) return pinn_launch_split_hp256(a, grid, stream, query, info);
-        if (nd == 2 && spec == 2) return (PINN_WIDE_TANH_STATIC && a->act == PINN_ACT_TANH) ? launch_one<2, 1, -1, PINN_ACT_TANH, PINN_WIDE_MT, true, 32 | WGXV>(a, grid, stream, query, info)
-                                                               : launch_one<2, 1, -1, -1, PINN_WIDE_MT, true, 32 | WGXV>(a, grid, stream, query, info);
+        if (nd == 2 && spec == 2 && a->gemm_mode == PINN_GEMM_BF16X3 && WGXV) return pinn_launch_split_hp256(a, req);
+        if (nd == 2 && spec == 2) return launch_wide_spec<2, PINN_VAR_SPEC(2) | WGXV>(a, req);
 #endif
 #define PINN_TRY_FAST_COMB(ND, LH, ACT, MT, VAR) \
-        if (nd == ND && a->lh == LH && a->act == ACT) return launch_one<ND, 1, LH, ACT, MT, true, VAR>(a, grid, stream, query, info);
+        if (nd == ND && a->lh == LH && a->act == ACT) return launch_one<ND, 1, LH, ACT, MT, true, VAR>(a, req);
         PINN_FAST_COMB_LIST(PINN_TRY_FAST_COMB)
 #undef PINN_TRY_FAST_COMB
-        if (nd == 2) return launch_one<2, 1, -1, -1, 1, true, WGXV>(a, grid, stream, query, info);
-        if (nd == 3) return launch_one<3, 1, -1, -1, 1, true, WGXV>(a, grid, stream, query, info);
-        if (nd == 4) return launch_one<4, 1, -1, -1, 1, true, WGXV>(a, grid, stream, query, info);       // 3-D space + time
+        if (nd == 2) return launch_one<2, 1, -1, -1, 1, true, WGXV>(a, req);
+        if (nd == 3) return launch_one<3, 1, -1, -1, 1, true, WGXV>(a, req);
+        if (nd == 4) return launch_one<4, 1, -1, -1, 1, true, WGXV>(a, req);       // 3-D space + time
         return 1;
     }
 #if PINN_INST_HP == 64
     // ODE-family shape of BASELINE config 4
 #if PINN_CHAIN
     if (nd == 1 && n2 == 0 && a->lh == 3 && a->act == PINN_ACT_TANH && spec == 3)
-        return launch_chain<1, 0, 3, PINN_CHAIN_MT_CFG4, false, 3>(a, grid, stream, query, info);
+        return launch_chain<1, 0, 3, PINN_CHAIN_MT_CFG4, false, 3>(a, req);
 #endif
     if (nd == 1 && n2 == 0 && a->lh == 3 && a->act == PINN_ACT_TANH && spec == 3 && a->gemm_mode == PINN_GEMM_BF16X3)
-        return pinn_launch_split_hp64_2(a, grid, stream, query, info);
+        return pinn_launch_split_hp64_2(a, req);
     if (nd == 1 && n2 == 0 && a->lh == 3 && a->act == PINN_ACT_TANH && spec == 3)
-        return launch_one<1, 0, 3, PINN_ACT_TANH, PINN_CFG4_MT, false, PINN_FAST_VAR_S2>(a, grid, stream, query, info);
+        return launch_one<1, 0, 3, PINN_ACT_TANH, PINN_CFG4_MT, false, PINN_FAST_VAR_S2>(a, req);
 #endif
     // (the S = 5 kernel of the 4 x 64 net -- residual programs, the generic path of config 2 -- measured with 32-point tiles: 0.349 ->
     //  0.445 ms, and as two workgroups per CU with W^T from the global copy: 0.381 ms; 16-point tiles, one workgroup per CU stay)
@@ -770,18 +723,18 @@ int PINN_CAT(pinn_launch_tile_hp, PINN_INST_HP)(int nd, int n2, const PinnKArgs*
         // fourth order (round 5; packed 73 = one direction with second, third and fourth derivative: beam / Kuramoto-Sivashinsky / biharmonic
         // operators, one such direction per call)
         if (skips && nd == 1 && n2 == 73) return PINN_BREADTH(1, 73, false);
-        if (nd == 1 && n2 == 73) return launch_one<1, 73, -1, -1, 1, false, WGXV>(a, grid, stream, query, info);
+        if (nd == 1 && n2 == 73) return launch_one<1, 73, -1, -1, 1, false, WGXV>(a, req);
         if (skips && nd == 1 && n2 == 9) return PINN_BREADTH(1, 9, false);
         if (skips && nd == 2 && n2 == 9) return PINN_BREADTH(2, 9, false);
-        if (nd == 1 && n2 == 9) return launch_one<1, 9, -1, -1, 1, false, WGXV>(a, grid, stream, query, info);
-        if (nd == 2 && n2 == 9) return launch_one<2, 9, -1, -1, 1, false, WGXV>(a, grid, stream, query, info);
+        if (nd == 1 && n2 == 9) return launch_one<1, 9, -1, -1, 1, false, WGXV>(a, req);
+        if (nd == 2 && n2 == 9) return launch_one<2, 9, -1, -1, 1, false, WGXV>(a, req);
         return 1;
     }
     const int key = nd * 4 + n2;          // (nd = 4 comes with n2 = 0 only: key 16)
     if (skips && plain_acts) {
         switch (key) {         // the commonest residual-program shapes of residual nets (others: the full breadth kernels below)
-            case 1 * 4 + 1: return launch_one<1, 1, -1, -1, 1, false, 8 | 1024 | WGXV>(a, grid, stream, query, info);
-            case 2 * 4 + 2: return launch_one<2, 2, -1, -1, 1, false, 8 | 1024 | WGXV>(a, grid, stream, query, info);
+            case 1 * 4 + 1: return launch_one<1, 1, -1, -1, 1, false, PINN_VAR_BREADTH | PINN_VAR_SKIPS_LIGHT | WGXV>(a, req);
+            case 2 * 4 + 2: return launch_one<2, 2, -1, -1, 1, false, PINN_VAR_BREADTH | PINN_VAR_SKIPS_LIGHT | WGXV>(a, req);
             default: break;
         }
     }
@@ -801,15 +754,15 @@ int PINN_CAT(pinn_launch_tile_hp, PINN_INST_HP)(int nd, int n2, const PinnKArgs*
         }
     }
     switch (key) {
-        case 0 * 4 + 0: return launch_one<0, 0, -1, -1, 1, false, WGXV>(a, grid, stream, query, info);
-        case 1 * 4 + 0: return launch_one<1, 0, -1, -1, 1, false, WGXV>(a, grid, stream, query, info);
-        case 1 * 4 + 1: return launch_one<1, 1, -1, -1, 1, false, WGXV>(a, grid, stream, query, info);
-        case 2 * 4 + 0: return launch_one<2, 0, -1, -1, 1, false, WGXV>(a, grid, stream, query, info);
-        case 2 * 4 + 2: return launch_one<2, 2, -1, -1, 1, false, WGXV>(a, grid, stream, query, info);
-        case 3 * 4 + 2: return launch_one<3, 2, -1, -1, 1, false, WGXV>(a, grid, stream, query, info);
-        case 4 * 4 + 0: return launch_one<4, 0, -1, -1, 1, false, WGXV>(a, grid, stream, query, info);
+        case 0 * 4 + 0: return launch_one<0, 0, -1, -1, 1, false, WGXV>(a, req);
+        case 1 * 4 + 0: return launch_one<1, 0, -1, -1, 1, false, WGXV>(a, req);
+        case 1 * 4 + 1: return launch_one<1, 1, -1, -1, 1, false, WGXV>(a, req);
+        case 2 * 4 + 0: return launch_one<2, 0, -1, -1, 1, false, WGXV>(a, req);
+        case 2 * 4 + 2: return launch_one<2, 2, -1, -1, 1, false, WGXV>(a, req);
+        case 3 * 4 + 2: return launch_one<3, 2, -1, -1, 1, false, WGXV>(a, req);
+        case 4 * 4 + 0: return launch_one<4, 0, -1, -1, 1, false, WGXV>(a, req);
 #if PINN_INST_HP <= 128
-        case 3 * 4 + 3: return launch_one<3, 3, -1, -1, 1, false, WGXV>(a, grid, stream, query, info);
+        case 3 * 4 + 3: return launch_one<3, 3, -1, -1, 1, false, WGXV>(a, req);
 #endif
         default: return 1;
     }

@@ -145,6 +145,34 @@ struct PinnKArgs {
     float crit_param;            // kernels only (PinnShape::crit); SmoothL1 beta / Huber delta. `inv_n` already is 1 for reduction='sum'
 };
 
+// ---- variant bits: the `int VAR` template parameter of pinn_tile_body / pinn_tile_kernel / pinn_fit_kernel ------------------------
+// (the parameter stays an int: kernel-name strings -- pinn_last_kernel_name, bench.py `kernel_variant` -- spell the sum of the bits.
+//  What each bit does is told where the kernel uses it; "requires / excludes" is what the static_asserts of pinn_tile_body and
+//  pinn_fit_kernel enforce; "built": does the default build instantiate a kernel with the bit?)
+//
+//  name                 value  turns on                                                   requires / excludes                          built
+//  PINN_VAR_DWG             1  dW in the partial buffer although the depth is static      excl. SPLIT, TEAMS2, SLAB_LDS                no
+//  PINN_VAR_2WG             2  two workgroups per CU, W^T from the global copy            excl. SPLIT (PINN_VAR2_REFUSED), TEAMS2      no
+//  PINN_VAR_NO_WPF          4  no whole-layer weight prefetch (widths <= 64)              --                                           no
+//  PINN_VAR_BREADTH         8  activation codes beyond Tanh / Sigmoid, skip connections   excl. SPLIT, TEAMS2, SLAB_LDS                yes
+//  PINN_VAR_SPEC(s)   s << 4   training shape s = 1 / 2 / 3 (PinnShape) fixed             --                                           yes
+//  PINN_VAR_SLAB_LDS       64  saved jets in LDS instead of the global slab               SPEC, static depth; excl. DWG, BREADTH, WGX  no
+//  PINN_VAR_WGX           128  hidden->hidden dW streamed to pinn_wgrad_kernel            generic depth (or DWG); excl. SLAB_LDS,      yes
+//                                                                                         TEAMS2; SPLIT at widths >= 128 requires it
+//  PINN_VAR_TEAMS2        256  two tile streams in one 8-wave workgroup                   SPEC, static depth, width 64; excl. DWG,     yes
+//                                                                                         2WG, BREADTH, SLAB_LDS, WGX
+//  PINN_VAR_SPLIT         512  split-bf16 hidden-layer GEMMs                              width 64: static depth, excl. DWG, 2WG,      yes
+//                                                                                         BREADTH, SLAB_LDS, WGX; widths >= 128: WGX,
+//                                                                                         excl. DWG, 2WG, BREADTH, SLAB_LDS, TEAMS2
+//  PINN_VAR_SKIPS_LIGHT  1024  BREADTH for skips over Tanh / Sigmoid layers only          BREADTH (no meaning without it)              yes
+//  PINN_VAR_PROGRAM      2048  residual program on a shape-specialised kernel             TEAMS2, SPEC, static depth; excl. SPLIT      yes
+//
+//  virtual workgroups (VW > 1) and pinn_fit_kernel: widths <= 32, excl. 2WG, SLAB_LDS, WGX, TEAMS2, SPLIT
+constexpr int PINN_VAR_DWG = 1, PINN_VAR_2WG = 2, PINN_VAR_NO_WPF = 4, PINN_VAR_BREADTH = 8, PINN_VAR_SLAB_LDS = 64, PINN_VAR_WGX = 128,
+              PINN_VAR_TEAMS2 = 256, PINN_VAR_SPLIT = 512, PINN_VAR_SKIPS_LIGHT = 1024, PINN_VAR_PROGRAM = 2048;
+PINN_HOST_DEVICE constexpr int PINN_VAR_SPEC(int s) { return s << 4; }
+PINN_HOST_DEVICE constexpr int pinn_var_spec(int var) { return (var >> 4) & 3; }
+
 template <int HP_, int ND_, int N2_, int MT_ = 1, bool SPLIT_ = false>
 struct PinnCfg {
     static constexpr int HP = HP_, ND = ND_, N2 = pinn_n2(N2_), N3 = pinn_n3(N2_), MT = MT_;
@@ -1418,23 +1446,23 @@ PINN_DEVICE void pinn_tile_body(const PinnKArgs& A, const float* params_, float*
     // workgroup's own copies (the one-CU form: in LDS); rstride_: the row stride of partials_ (A.p_core / rounded up to 16 bytes)
     // (the body of the tile kernel as a function: pinn_tile_kernel below runs it once per launch, pinn_fit_kernel.h -- a whole chunk of
     //  fit iterations in one launch, round 5 -- once per iteration)
-    using C = PinnCfg<HP, ND, N2, MT, (VAR & 512) != 0>;
+    using C = PinnCfg<HP, ND, N2, MT, (VAR & PINN_VAR_SPLIT) != 0>;
     constexpr int S = C::S, NT = C::NT, NTW = C::NTW, NW = C::NW, T = C::T, LDA = C::LDA, NTHREADS = C::NTHREADS;
     // (only the one-CU fit chunk has copies of its own: everybody else reads the launch arguments where they are needed -- as values
     //  carried through the whole kernel the three cost BASELINE config 2's kernel 0.8 %, same-box A/B)
     const float* xs_ = (VW > 1) ? xs_in : A.xs;
     float* aux_ = (VW > 1) ? aux_in : A.aux;
     const int rstride_ = (VW > 1) ? rstride_in : A.p_core;
-    constexpr bool DWG = (LHC < 0) || (VAR & 1), ONEBUF = C::ONEBUF, SKIPS = (VAR & 8) != 0;
+    constexpr bool DWG = (LHC < 0) || (VAR & PINN_VAR_DWG), ONEBUF = C::ONEBUF, SKIPS = (VAR & PINN_VAR_BREADTH) != 0;
     constexpr int LHREG = DWG ? 1 : PINN_LHMAX;            // layers with register-resident dW accumulators
     // VAR 64: saved jets in LDS instead of the global slab (no slab traffic at all); W^T then lives in the workgroup's own
     // global scratch, written in the prologue (the LDS it used to occupy is what the jets need)
-    constexpr bool SLABL = (VAR & 64) != 0;
-    constexpr bool WGX = (VAR & 128) != 0;
-    constexpr bool TEAMS2 = (VAR & 256) != 0;
+    constexpr bool SLABL = (VAR & PINN_VAR_SLAB_LDS) != 0;
+    constexpr bool WGX = (VAR & PINN_VAR_WGX) != 0;
+    constexpr bool TEAMS2 = (VAR & PINN_VAR_TEAMS2) != 0;
     constexpr bool VWG = VW > 1;                           // virtual workgroups (above): `team` is the virtual workgroup's index
     constexpr int TEAMS = TEAMS2 ? 2 : VW;
-    static_assert(!VWG || (!TEAMS2 && !(VAR & (2 | 64 | 128 | 512)) && NW <= 2 && HP <= 32), "virtual workgroups: the narrow nets' plain kernels");
+    static_assert(!VWG || (!TEAMS2 && !(VAR & (PINN_VAR_2WG | PINN_VAR_SLAB_LDS | PINN_VAR_WGX | PINN_VAR_SPLIT)) && NW <= 2 && HP <= 32), "virtual workgroups: the narrow nets' plain kernels");
     // VAR 512: split-bf16 GEMMs. Every hidden-layer GEMM (forward, data gradient, weight gradient) runs on
     // v_mfma_f32_16x16x32_bf16 with both operands split exactly into hi + mid + lo bf16 and the six products a_i b_j,
     // i + j <= 2, accumulated in fp32 (pinn_mfma_split6): 6 x 16 cycles of the matrix pipe per K = 32 instead of 8 x 32 cycles
@@ -1455,34 +1483,36 @@ PINN_DEVICE void pinn_tile_body(const PinnKArgs& A, const float* params_, float*
     // Widths >= 128 (round 3, later): the WGX form -- forward and data-gradient GEMMs here, weight fragments streamed K block by
     // K block (they do not fit the registers), weight gradients in pinn_wgrad_kernel's own split form.
 #ifndef PINN_VAR2_REFUSED
-#define PINN_VAR2_REFUSED 2     // (0 in the experiment builds that look for the cause of the finding above)
+#define PINN_VAR2_REFUSED PINN_VAR_2WG     // (0 in the experiment builds that look for the cause of the finding above)
 #endif
-    static_assert(!SPLIT || (HP == 64 && NTW == 1 && LHC >= 1 && !(VAR & (1 | PINN_VAR2_REFUSED | 8 | 64 | 128)) && ((S * T) % 32) == 0 &&
+    static_assert(!SPLIT || (HP == 64 && NTW == 1 && LHC >= 1 && !(VAR & (PINN_VAR_DWG | PINN_VAR2_REFUSED | PINN_VAR_BREADTH | PINN_VAR_SLAB_LDS | PINN_VAR_WGX)) &&
+                             ((S * T) % 32) == 0 &&
                              ((T == 16 && S % 2 == 0) || T == 32)) ||
-                            (HP >= 128 && (VAR & 128) && !(VAR & (1 | 2 | 8 | 64 | 256))),
+                            (HP >= 128 && (VAR & PINN_VAR_WGX) && !(VAR & (PINN_VAR_DWG | PINN_VAR_2WG | PINN_VAR_BREADTH | PINN_VAR_SLAB_LDS | PINN_VAR_TEAMS2))),
                   "split-bf16 kernels: width 64 with static depth and register-resident dW (K = S * T a multiple of 32), or the WGX kernels of widths >= 128");
     constexpr bool SPW = SPLIT && HP >= 128;               // wide form: weights streamed inside the GEMM
     constexpr int SPK = (SPLIT && !SPW) ? C::SP_KB : 1;    // K blocks whose weight fragments a wave holds at once (width 64: all)
-    static_assert(!TEAMS2 || (((VAR >> 4) & 3) != 0 && LHC >= 1 && !(VAR & (1 | 2 | 8 | 64 | 128)) && NW == 4 && C::wt_fits_teams(LHC)),
+    static_assert(!TEAMS2 || (pinn_var_spec(VAR) != 0 && LHC >= 1 && !(VAR & (PINN_VAR_DWG | PINN_VAR_2WG | PINN_VAR_BREADTH | PINN_VAR_SLAB_LDS | PINN_VAR_WGX)) &&
+                              NW == 4 && C::wt_fits_teams(LHC)),
                   "two-team kernels: shape-specialised, static depth, 4 waves per team, W^T of all layers in LDS");
     constexpr bool SNT = HP >= PINN_SLAB_NT_MIN_HP;        // streaming (non-temporal) slab stores
     static_assert(!WGX || (DWG && !SLABL), "WGX kernels: generic depth, global slab");
-    static_assert(!SLABL || (((VAR >> 4) & 3) != 0 && LHC >= 1 && !(VAR & 8) && !(VAR & 1) && C::slabl_fits(LHC)),
+    static_assert(!SLABL || (pinn_var_spec(VAR) != 0 && LHC >= 1 && !(VAR & PINN_VAR_BREADTH) && !(VAR & PINN_VAR_DWG) && C::slabl_fits(LHC)),
                   "slab-in-LDS kernels: shape-specialised, static depth, no skips, and the jets must fit");
-    constexpr bool WTL = !SPLIT && ((C::wt_fits(LHC) && !SLABL && !(VAR & 2)) || TEAMS2);        // transposed hidden weights staged in LDS
+    constexpr bool WTL = !SPLIT && ((C::wt_fits(LHC) && !SLABL && !(VAR & PINN_VAR_2WG)) || TEAMS2);        // transposed hidden weights staged in LDS
     // (virtual workgroups: C::wt_fits(LHC) of ONE block is the launcher's condition for the shared copy as well -- pinn_inst.inc sizes
     //  VW so that VW blocks + W^T fit)
     // widths >= 128: the data-gradient A operand comes from a transposed copy of the weights in global memory (one b128 per
     // K quad like the forward GEMM) instead of four strided global_load_dword per quad
     // (VAR 2, two workgroups per CU: W^T of both does not fit the LDS beside the activation buffers)
-    constexpr bool WTG = !SPLIT && (C::WTG || SLABL || (VAR & 2) != 0);
-    constexpr int SPEC = (VAR >> 4) & 3;                   // VAR 16/32/48: training shape 1/2/3 fixed at compile time
+    constexpr bool WTG = !SPLIT && (C::WTG || SLABL || (VAR & PINN_VAR_2WG) != 0);
+    constexpr int SPEC = pinn_var_spec(VAR);                   // VAR 16/32/48: training shape 1/2/3 fixed at compile time
     // VAR 2048 (round 6): the shape-specialised two-team kernel with a residual PROGRAM (PinnShape: SPEC | 4) -- its program registers
     // (PINN_MAX_REGS values + adjoints per point of a team's tile) live in the rows of the team's bias-gradient block that a static-depth
     // net never uses (rows 8 .. PINN_MAX_LAYERS - 1 of `accB`: the team blocks of the LDS carve end in front of the program registers,
     // and with W^T behind them the 160 KB are used up); the point stage runs on the first T threads of the team (every lane running it,
     // PTALL, would have sixteen replicas add into the same adjoint registers)
-    constexpr bool PROG = (VAR & 2048) != 0;
+    constexpr bool PROG = (VAR & PINN_VAR_PROGRAM) != 0;
     constexpr int SPECP = SPEC | (PROG ? 4 : 0);
     using SH = PinnShape<SPECP, ND>;
     static_assert(!PROG || (TEAMS2 && SPEC != 0 && LHC >= 1 && LHC + 1 <= 8 && !SPLIT &&
@@ -1506,7 +1536,7 @@ PINN_DEVICE void pinn_tile_body(const PinnKArgs& A, const float* params_, float*
     //  sin / softplus / SiLU / GELU paths compiled in, the width-128 breadth kernel spills 283 registers and runs 8 % slower)
     // skips that START in front of an activation ('fRa'): the generic-depth full breadth kernels only (the selects and the guarded slab
     // reads cost the static-depth Sin kernel 3.5 % -- 9 % with the guard inside the jet loop -- and it never sees a skip)
-    constexpr bool SRCPRE = SKIPS && !(VAR & 1024) && LHC < 0;
+    constexpr bool SRCPRE = SKIPS && !(VAR & PINN_VAR_SKIPS_LIGHT) && LHC < 0;
     // nested skips (round 5): the same kernels. ONE skip rides in registers (`hskip`); a skip during whose life another one opens
     // ("outer", A.skip_outer) parks its jets in its own slab slot at 'R' and reads them back at '+' -- lane-private, written and
     // read by the same lane, L2-resident -- so that nesting costs no second register set (the launcher sends nested nets here)
@@ -1524,7 +1554,7 @@ PINN_DEVICE void pinn_tile_body(const PinnKArgs& A, const float* params_, float*
     // (the parameter of a configured LeakyReLU / ELU / Softplus travels with the code in the full breadth kernels -- round 6)
     auto act_at = [&](int a) -> PinnAct {
         if (ACTC >= 0) return PinnAct(ACTK);
-        constexpr bool FULL = SKIPS && !(VAR & 1024);
+        constexpr bool FULL = SKIPS && !(VAR & PINN_VAR_SKIPS_LIGHT);
         return PinnAct(pinn_act_code(A.act_codes, a) & (FULL ? (ALLACT ? 15 : 7) : 1), FULL ? A.act_par[a] : 0.0f);
     };
     auto with_poly = [&](PinnAct a) -> PinnAct { return PinnAct(a.c | TPOLY, a.p); };
@@ -1545,7 +1575,7 @@ PINN_DEVICE void pinn_tile_body(const PinnKArgs& A, const float* params_, float*
 
     PINN_SMEM(smem_all);
     // (virtual workgroups of a kernel with program registers carry them in their block; W^T sits once behind all blocks)
-    constexpr int TEAM_FLOATS = (VWG && ((VAR >> 4) & 3) == 0) ? C::SMEM_FLOATS : C::TEAM_FLOATS;
+    constexpr int TEAM_FLOATS = (VWG && pinn_var_spec(VAR) == 0) ? C::SMEM_FLOATS : C::TEAM_FLOATS;
     float* smem = smem_all + team * TEAM_FLOATS;               // (one team: the whole block)
     float* xs_base = smem + C::O_XS;
     float* W1s = smem + C::O_W1;
@@ -1619,7 +1649,7 @@ PINN_DEVICE void pinn_tile_body(const PinnKArgs& A, const float* params_, float*
             wt_write(e0, wreg);
         }
     }
-    if (!SLABL && !TEAMS2 && !(VWG && ((VAR >> 4) & 3) != 0))
+    if (!SLABL && !TEAMS2 && !(VWG && pinn_var_spec(VAR) != 0))
         for (int i = tid; i < PINN_MAX_REGS * T; i += NTHREADS) padj[i] = 0.0f;   // (team blocks end before the program registers)
     const float bL = params_[A.off_bl];
 
@@ -1660,10 +1690,10 @@ PINN_DEVICE void pinn_tile_body(const PinnKArgs& A, const float* params_, float*
 #endif
     // (register accumulators for the bias / first-layer gradients in the two-streams-per-CU kernels as well: 80-160 B per lane of
     //  scratch, slower -- DESIGN.md section 6a)
-    constexpr bool REGB = !DWG && !(VAR & (2 | 256)) && (S * MT * NTW <= (SPEC != 0 ? PINN_REGB_MAX_SPEC : PINN_REGB_MAX));
+    constexpr bool REGB = !DWG && !(VAR & (PINN_VAR_2WG | PINN_VAR_TEAMS2)) && (S * MT * NTW <= (SPEC != 0 ? PINN_REGB_MAX_SPEC : PINN_REGB_MAX));
     // (two workgroups per CU live on 256 registers: accumulators for the layers that exist and two input columns only)
-    constexpr int W1R = (VAR & (2 | 256)) ? 2 : 4;
-    constexpr int NBR = (VAR & (2 | 256)) && LHC >= 0 ? LHC + 1 : PINN_LHMAX + 1;
+    constexpr int W1R = (VAR & (PINN_VAR_2WG | PINN_VAR_TEAMS2)) ? 2 : 4;
+    constexpr int NBR = (VAR & (PINN_VAR_2WG | PINN_VAR_TEAMS2)) && LHC >= 0 ? LHC + 1 : PINN_LHMAX + 1;
     f32x4 accBr[REGB ? NBR : 1][NTW], accW1r[REGB ? W1R : 1][NTW];
 #pragma unroll
     for (int j = 0; j < NTW; ++j) {
@@ -1987,7 +2017,7 @@ PINN_DEVICE void pinn_tile_body(const PinnKArgs& A, const float* params_, float*
         // (not in the VAR 8 kernels: with the four-way activation code between the prefetch and its first use, hipcc
         //  7.2 produced a width-64 kernel whose last prefetched K quad arrived wrong on gfx950 -- reproducible, cured by
         //  -amdgpu-waitcnt-forcezero, by dropping the prefetch, or by the two-way activation)
-        constexpr bool WPF = (HP <= 64) && !(VAR & 4) && !(VAR & 8) && !SPLIT;
+        constexpr bool WPF = (HP <= 64) && !(VAR & PINN_VAR_NO_WPF) && !(VAR & PINN_VAR_BREADTH) && !SPLIT;
         constexpr int NQ = HP / 16;
         f32x4 wall[WPF ? NQ : 1][NTW];
         f32x4 biasn[NTW];              // bias of the NEXT hidden layer, fetched with its weights
@@ -2417,7 +2447,7 @@ PINN_DEVICE void pinn_tile_body(const PinnKArgs& A, const float* params_, float*
 #ifndef PINN_SVPF_WIDE_MAX
 #define PINN_SVPF_WIDE_MAX 4       // 8-wave kernels: registers first -- only the shape-specialised ones with S <= 4 streams at width 128 have
 #endif                             // room (same-box A/B, round 4: skip128 tile kernel -1.2 %; the S = 5 kernel of config 3 spills and loses 4 %)
-        constexpr bool SVPF = (S * MT * NTW <= ((NW <= 4) ? PINN_SVPF_MAX : ((VAR & 48) ? PINN_SVPF_WIDE_MAX : 0))) && !ONEBUF;
+        constexpr bool SVPF = (S * MT * NTW <= ((NW <= 4) ? PINN_SVPF_MAX : (pinn_var_spec(VAR) ? PINN_SVPF_WIDE_MAX : 0))) && !ONEBUF;
         if (SVPF && lh > 0) load_saved(lh - 1, svn);
 #pragma unroll
         for (int j = 0; j < NTW; ++j) {
@@ -3167,8 +3197,8 @@ PINN_DEVICE void pinn_tile_body(const PinnKArgs& A, const float* params_, float*
 }
 
 template <int HP, int ND, int N2, int MT, int LHC, int ACTC, bool COMB = false, int VAR = 0>
-PINN_GLOBAL void PINN_LAUNCH_BOUNDS2((PinnCfg<HP, ND, N2, MT>::NTHREADS * ((VAR & 256) ? 2 : 1)),
-                                    (PinnCfg<HP, ND, N2, MT>::NW < 4 || (VAR & (2 | 256)) ? 2 : PINN_WAVES_PER_SIMD))
+PINN_GLOBAL void PINN_LAUNCH_BOUNDS2((PinnCfg<HP, ND, N2, MT>::NTHREADS * ((VAR & PINN_VAR_TEAMS2) ? 2 : 1)),
+                                    (PinnCfg<HP, ND, N2, MT>::NW < 4 || (VAR & (PINN_VAR_2WG | PINN_VAR_TEAMS2)) ? 2 : PINN_WAVES_PER_SIMD))
 pinn_tile_kernel(const PinnKArgs A) {
     pinn_tile_body<HP, ND, N2, MT, LHC, ACTC, COMB, VAR>(A, A.params, A.partials, A.xs, A.aux, A.p_core);
 }

@@ -536,6 +536,27 @@ def test_grid_form_every_iteration_and_every_split_on_the_gpu(pa, gpu_lib, monke
     _case_a(pa, {}, gpu_lib, monkeypatch, 'gpu_fit_chunk_grid', 100, persist=1)
 
 
+def test_declined_chunk_leaves_no_timeout_flag_of_an_earlier_chunk_on_the_emulator(pa, emu_lib, monkeypatch):
+    """ pinn_fit_chunk_status reads the flag of the LAST grid-form chunk of the thread. A later chunk that declines the one-launch form must
+    not leave it pointing at the earlier chunk's flag: that workspace memory has another use by then. (One tile: the emulator runs the grid
+    form on a grid of one workgroup.) The workspace stays allocated throughout; nothing is freed. """
+    _env(monkeypatch, 1, 4)
+    run = Run(pa, _emu(pa, emu_lib, monkeypatch), emu_lib, 'ode_16', TILE, SEEDS['ode_16'])
+    kernel = run.fit(1)
+    assert kernel.startswith('pinn_fit_kernel<') and _vw(kernel) == 1, kernel          # the grid form
+    assert emu_lib.pinn_fit_chunk_status() == 0
+    workspaces = list(run.solver.model._workspaces.values())
+    assert workspaces
+    for ws in workspaces:
+        ws.view(torch.uint8).fill_(0xA5)
+    monkeypatch.setenv('PYDENS_AMD_FIT_PERSIST', '2')       # (Solver.fit asks for the status itself under '1')
+    net = run.solver.model.net
+    assert net.lib.pinn_debug_fit_persistent(net.handle, 0) == 1
+    kernel = run.fit(1)
+    assert kernel.startswith('pinn_tile_kernel<'), kernel                               # declined: the launch graphs
+    assert emu_lib.pinn_fit_chunk_status() == 0
+
+
 # (room: registers the in-kernel pre-pass holds = PinnCfg::PREPASS_FLOATS_PER_LANE / 2 of the problem's kernel)
 WIDE_ROOM = {'wide_prepass_16': 24}
 
