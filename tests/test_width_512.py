@@ -148,7 +148,7 @@ def _reference(name, problem, seed, n, chunk=None, relu=False, fp32=True):
         o64 = po.OracleSolver(eq, dtype=torch.float64, **kw)
         start = o32.export_params()
         o64.import_params(start)
-        pts = _points(n, kw['ndims'])
+        pts = _points(n, kw['ndims'] + kw.get('nparams', 0))           # (parameter columns: test_width_128_256.py)
         gap, hooks = [np.inf], []
         if relu:            # smallest |pre-activation| of any ReLU layer over the batch, in fp64
             for m in o64.model.conv_block:
