@@ -551,6 +551,45 @@ int pinn_balance_terms(const float* term_grads, int64_t ld, int32_t n_terms, int
                        int32_t ref_term, int32_t update, double momentum, double lo, double hi, void* state, size_t state_bytes,
                        float* grads_out, float* term_loss_out, float* weight_out, void* workspace, size_t workspace_bytes, void* stream);
 
+/* Causal training weights (Wang, Sankaran, Perdikaris 2022) over time bins of a batch -- three launches whatever n and the number of
+ * bins (pydens_amd/csrc/pinn_causal_kernels.h: bin statistics, the rule by one workgroup, one pass that hands every point its weight).
+ * Definition. n points with times t_i = t[i * t_stride] (fp32; t_stride in [1, PINN_CAUSAL_MAX_STRIDE] lets t be a column of a row-major
+ * [n][d] point buffer; n up to 2^30: every byte offset then stays far inside 64 bits),
+ * the time domain t_lo < t_hi, `bins` = M bins, 1 <= M <= PINN_CAUSAL_MAX_BINS, residuals r [n] (fp32), a tolerance eps >= 0:
+ *   bin          k(i) = clamp(floor((double(t_i) - t_lo) / (t_hi - t_lo) * M), 0, M - 1), in fp64 with exactly this association: t_hi
+ *                itself and everything outside the domain land in the end bins, a NaN t_i in bin 0
+ *   statistics   n_k = points in bin k; L_k = (sum over the bin of double(r_i)^2) / n_k, 0 for an empty bin. A non-finite r_i adds 0 to
+ *                the sum, still counts in n_k, and sets the non_finite flag of the state (the rule of pinn_resample_points)
+ *   bin weight   w_k = exp(-eps * P_k) in fp64, P_k = sum_{j<k} L_j in ascending j: w_0 = 1, the weights never increase with k. An
+ *                eps * P_k large enough to underflow gives exactly 0.0, never NaN (also eps * inf); eps == 0 gives exactly 1.0 everywhere
+ *   point weight w_out[i] = fl32(w_{k(i)})
+ * The weighted equation term of a loss is mean_i w_out[i] * r_i^2 with the weights held constant (stop-gradient, as in the paper); it
+ * equals sum_k (n_k / n) w_k L_k, the paper's 1/M sum_k w_k L_k where the bins are equally filled.
+ * The tolerance ladder (the paper's annealing) is decided on the device: the state holds up to PINN_CAUSAL_MAX_EPS tolerances and an
+ * index. A call computes its weights with the tolerance at the index; then, if update != 0 and min_k w_k > delta, the index moves up by
+ * one for the NEXT call -- at the last tolerance `converged` is set instead and the index stays. delta >= 1 never advances.
+ *   state        pinn_causal_state_bytes, doubles: [0..8) the ladder  [8] its length  [9] the index  [10] delta  [11] converged
+ *                [12] non_finite: 1 once a call since init met a NaN or infinite residual  [13] calls so far  [14] the tolerance of the
+ *                last call  [15] its unweighted mean r^2, and the last call's bins: [16..80) n_k  [80..144) L_k  [144..208) w_k (zero
+ *                from `bins` on). pinn_causal_init fills it: the ladder (host memory, 1 to 8 tolerances, finite, >= 0) and delta
+ *                (any number, not NaN), everything else zero
+ *   w_out        [n] floats, required. bin_weight_out [bins], eps_out [1], mean_sq_out [1]: floats or null, written by the second launch
+ *                (as loss_out of the optimizer entry points is): fl32(w_k), the tolerance used, the unweighted mean r^2 of the batch
+ *   workspace    rows of partial statistics, the size the workspace_bytes query returns
+ * state and workspace 16-byte aligned. No output may overlap t, r, the state, the workspace or another output. Bit-repeatable: no
+ * atomics, fixed summation orders (per bin: the lanes of a wave in order, the four waves, the chunks of a workgroup, the workgroups).
+ * n_k is exact; L_k carries fp64 rounding only (a product of two fp32 values is exact in fp64). n == 0 succeeds and launches nothing
+ * (the state stays). Nothing synchronises and nothing is read back. A refused call (non-zero, pinn_last_error) has launched nothing. */
+#define PINN_CAUSAL_MAX_BINS 64
+#define PINN_CAUSAL_MAX_EPS 8
+#define PINN_CAUSAL_MAX_STRIDE (1 << 20)
+size_t pinn_causal_state_bytes(void);
+size_t pinn_causal_workspace_bytes(int64_t n, int32_t bins);
+int pinn_causal_init(void* state, size_t state_bytes, const double* eps_ladder, int32_t n_eps, double delta, void* stream);
+int pinn_causal_weights(const float* t, int64_t t_stride, const float* r, int64_t n, int32_t bins, double t_lo, double t_hi, int32_t update,
+                        void* state, size_t state_bytes, float* w_out, float* bin_weight_out, float* eps_out, float* mean_sq_out,
+                        void* workspace, size_t workspace_bytes, void* stream);
+
 /* Residual-adaptive collocation sampling (RAD: Wu et al., CMAME 2023): n_out rows of `pool` [m][d] (fp32, row-major, d <= 8,
  * m <= 2^22) drawn with replacement with probability proportional to q_i = w_i + floor_c * mean(w), w_i = |r_i|^power in double
  * (power 1 or 2; a non-finite r_i has weight 0), mean(w) = sum(w) / m.  Inverse CDF over the inclusive fp64 prefix sums P of q:

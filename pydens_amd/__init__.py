@@ -9,6 +9,7 @@ from .tokens import D, V, current_model
 from .model import TorchModel, ConvBlockModel
 from .solver import Solver
 from .balance import LossBalancer
+from .causal import CausalWeights
 from .sampler import *            # noqa: F401,F403  (reference re-exports batchflow.sampler.*)
 from .sampler import NumpySampler, NS, Sampler, ConstantSampler, ResidualSampler
 

@@ -6,6 +6,7 @@
 #include "pinn_port_probe.h"
 #include "pinn_lbfgs_kernels.h"
 #include "pinn_balance_kernels.h"
+#include "pinn_causal_kernels.h"
 
 #include <atomic>
 #include <cfloat>
@@ -1573,6 +1574,98 @@ int pinn_balance_terms(const float* term_grads, int64_t ld, int32_t n_terms, int
         launch("loss-weight kernel", pinn_balance_finalize_kernel, 1, PINN_BALANCE_THREADS, rowlen * sizeof(double), stream, A))
         return 1;
     return launch("loss-weight kernel", pinn_balance_combine_kernel, blocks, PINN_BALANCE_THREADS, 0, stream, A);
+}
+
+// ---- causal training weights (pinn_causal_kernels.h): three launches per call, whatever n and the number of bins -----------------------
+static_assert(PINN_CAUSAL_STATE_DOUBLES % 2 == 0, "the state block is a whole number of 16-byte pieces");
+#define PINN_CAUSAL_MAX_POINTS ((int64_t)1 << 30)
+
+// chunks of 256 points per workgroup of the stats pass, and the workgroups (= rows of partials) that gives
+static void causal_fold(int64_t n, int* chunks, int* rows) {
+    const int64_t all = (n + PINN_CAUSAL_THREADS - 1) / PINN_CAUSAL_THREADS;
+    *chunks = (int)((all + PINN_CAUSAL_MAX_ROWS - 1) / PINN_CAUSAL_MAX_ROWS);
+    *rows = (int)((all + *chunks - 1) / *chunks);
+}
+
+static bool causal_overlap(const void* a, size_t a_bytes, const void* b, size_t b_bytes) {
+    const uintptr_t a0 = reinterpret_cast<uintptr_t>(a), b0 = reinterpret_cast<uintptr_t>(b);
+    return a && b && a0 < b0 + b_bytes && b0 < a0 + a_bytes;
+}
+
+size_t pinn_causal_state_bytes(void) { return (size_t)PINN_CAUSAL_STATE_DOUBLES * sizeof(double); }
+
+size_t pinn_causal_workspace_bytes(int64_t n, int32_t bins) {
+    if (n < 0 || n > PINN_CAUSAL_MAX_POINTS || bins < 1 || bins > PINN_CAUSAL_MAX_BINS) return 0;
+    int chunks = 1, rows = 1;
+    if (n > 0) causal_fold(n, &chunks, &rows);
+    return (size_t)rows * (size_t)PINN_CAUSAL_ROWLEN(bins) * sizeof(double);
+}
+
+int pinn_causal_init(void* state, size_t state_bytes, const double* eps_ladder, int32_t n_eps, double delta, void* stream) {
+    if (!state || !eps_ladder) return fail("causal weights: null argument");
+    if (n_eps < 1 || n_eps > PINN_CAUSAL_MAX_EPS) return fail("causal weights: a ladder of %d tolerances; 1 to %d", n_eps, PINN_CAUSAL_MAX_EPS);
+    if (reinterpret_cast<uintptr_t>(state) & 15) return fail("causal weights: the state block must be 16-byte aligned");
+    if (state_bytes < pinn_causal_state_bytes())
+        return fail("causal weights: state block too small (%zu < %zu bytes)", state_bytes, pinn_causal_state_bytes());
+    if (delta != delta) return fail("causal weights: delta is not a number");
+    PinnCausalArgs A = {};
+    A.state = static_cast<double*>(state); A.n_eps = n_eps; A.delta = delta;
+    for (int j = 0; j < n_eps; ++j) {
+        if (!(eps_ladder[j] >= 0.0 && eps_ladder[j] <= DBL_MAX))
+            return fail("causal weights: tolerance %d is %g; a tolerance is finite and not negative", j, eps_ladder[j]);
+        A.ladder[j] = eps_ladder[j];
+    }
+    return launch("causal-weight kernel", pinn_causal_init_kernel, 1, PINN_CAUSAL_THREADS, 0, stream, A);
+}
+
+int pinn_causal_weights(const float* t, int64_t t_stride, const float* r, int64_t n, int32_t bins, double t_lo, double t_hi, int32_t update,
+                        void* state, size_t state_bytes, float* w_out, float* bin_weight_out, float* eps_out, float* mean_sq_out,
+                        void* workspace, size_t workspace_bytes, void* stream) {
+    if (bins < 1 || bins > PINN_CAUSAL_MAX_BINS) return fail("causal weights: bins=%d outside [1, %d]", bins, PINN_CAUSAL_MAX_BINS);
+    if (n < 0 || n > PINN_CAUSAL_MAX_POINTS) return fail("causal weights: n=%lld points outside [0, %lld]", (long long)n, (long long)PINN_CAUSAL_MAX_POINTS);
+    if (!t || !r || !state || !w_out || !workspace) return fail("causal weights: null argument");
+    if (t_stride < 1 || t_stride > PINN_CAUSAL_MAX_STRIDE)
+        return fail("causal weights: t_stride=%lld (floats between two times) outside [1, %lld]", (long long)t_stride, (long long)PINN_CAUSAL_MAX_STRIDE);
+    if (!(t_lo < t_hi && t_lo >= -DBL_MAX && t_hi <= DBL_MAX))
+        return fail("causal weights: the time domain [%g, %g] must be finite with t_lo < t_hi", t_lo, t_hi);
+    if ((reinterpret_cast<uintptr_t>(state) | reinterpret_cast<uintptr_t>(workspace)) & 15)
+        return fail("causal weights: state and workspace must be 16-byte aligned");
+    const void* floats[] = {t, r, w_out, bin_weight_out, eps_out, mean_sq_out};
+    for (const void* p : floats)
+        if (reinterpret_cast<uintptr_t>(p) & 3) return fail("causal weights: float buffers must be 4-byte aligned");
+    if (state_bytes < pinn_causal_state_bytes())
+        return fail("causal weights: state block too small (%zu < %zu bytes)", state_bytes, pinn_causal_state_bytes());
+    if (workspace_bytes < pinn_causal_workspace_bytes(n, bins))
+        return fail("causal weights: workspace too small (%zu < %zu bytes)", workspace_bytes, pinn_causal_workspace_bytes(n, bins));
+    // what the launches read, and what they write: no output may lie over an input, the state, the workspace or another output
+    const size_t n_ = (size_t)n, t_bytes = n ? ((n_ - 1) * (size_t)t_stride + 1) * sizeof(float) : 0;
+    const struct { const void* p; size_t bytes; const char* name; } outs[] = {
+        {w_out, n_ * sizeof(float), "w_out"}, {bin_weight_out, (size_t)bins * sizeof(float), "bin_weight_out"},
+        {eps_out, sizeof(float), "eps_out"}, {mean_sq_out, sizeof(float), "mean_sq_out"}};
+    const struct { const void* p; size_t bytes; const char* name; } ins[] = {
+        {t, t_bytes, "t"}, {r, n_ * sizeof(float), "r"}, {state, pinn_causal_state_bytes(), "the state"},
+        {workspace, pinn_causal_workspace_bytes(n, bins), "the workspace"}};
+    for (int a = 0; a < 4; ++a) {
+        for (const auto& in : ins)
+            if (causal_overlap(outs[a].p, outs[a].bytes, in.p, in.bytes)) return fail("causal weights: %s overlaps %s", outs[a].name, in.name);
+        for (int b = a + 1; b < 4; ++b)
+            if (causal_overlap(outs[a].p, outs[a].bytes, outs[b].p, outs[b].bytes))
+                return fail("causal weights: %s overlaps %s", outs[a].name, outs[b].name);
+    }
+    if (n == 0) return 0;                       // (nothing at all: the state stays as it is)
+    PinnCausalArgs A = {};
+    A.t = t; A.t_stride = (long long)t_stride; A.r = r; A.n = (long long)n; A.M = bins; A.update = update ? 1 : 0;
+    A.t_lo = t_lo; A.t_hi = t_hi;
+    A.state = static_cast<double*>(state); A.rows = static_cast<double*>(workspace);
+    causal_fold(n, &A.chunks, &A.n_rows);
+    A.w_out = w_out; A.bin_weight_out = bin_weight_out; A.eps_out = eps_out; A.mean_sq_out = mean_sq_out;
+    const size_t smem_stats = PINN_CAUSAL_THREADS * (2 * sizeof(double) + 3 * sizeof(int));
+    const size_t smem_rule = 2 * PINN_CAUSAL_MAX_BINS * sizeof(double) + 16;
+    const int blocks = (int)((n + PINN_CAUSAL_THREADS - 1) / PINN_CAUSAL_THREADS);
+    if (launch("causal-weight kernel", pinn_causal_stats_kernel, A.n_rows, PINN_CAUSAL_THREADS, smem_stats, stream, A) ||
+        launch("causal-weight kernel", pinn_causal_rule_kernel, 1, PINN_CAUSAL_THREADS, smem_rule, stream, A))
+        return 1;
+    return launch("causal-weight kernel", pinn_causal_apply_kernel, blocks, PINN_CAUSAL_THREADS, 0, stream, A);
 }
 
 // ---- residual-adaptive resampler (pinn_aux_kernels.h: three launches; the redraw is the third alone) -----------------------------------

@@ -28,6 +28,10 @@ BALANCE_MAX_TERMS = 8                                              # include/pin
 BALANCE_FIXED, BALANCE_MAX_MEAN, BALANCE_NORM = 0, 1, 2            # include/pinn.h PINN_BALANCE_*: `kind` of pinn_balance_terms
 # pinn_balance_terms' state block, in doubles: (first, count) of every field
 BALANCE_STATE = dict(weights=(0, 8), updates=(8, 1), count=(9, 1), gmax=(16, 8), sum_abs=(24, 8), sum_sq=(32, 8), non_finite=(40, 8))
+CAUSAL_MAX_BINS, CAUSAL_MAX_EPS = 64, 8                              # include/pinn.h PINN_CAUSAL_MAX_BINS / PINN_CAUSAL_MAX_EPS
+# pinn_causal_weights' state block, in doubles: (first, count) of every field
+CAUSAL_STATE = dict(ladder=(0, 8), n_eps=(8, 1), index=(9, 1), delta=(10, 1), converged=(11, 1), non_finite=(12, 1), calls=(13, 1),
+                    eps=(14, 1), mean_sq=(15, 1), bin_count=(16, 64), bin_loss=(80, 64), bin_weight=(144, 64))
 SKIP_PRE = 0x100         # include/pinn.h PINN_SKIP_PRE
 ACT_CODES = {'tanh': 0, 'sigmoid': 1, 'sin': 2, 'identity': 3, 'softplus': 4, 'silu': 5, 'swish': 5, 'gelu': 6,
              # round 5 (include/pinn.h PINN_ACT_RELU ..): torch-default forms
@@ -196,6 +200,14 @@ def bind(lib):
     lib.pinn_balance_terms.argtypes = [vp, i64, i32, i64, vp, i32, i32, i32, i32, f64, f64, f64, vp, ctypes.c_size_t, vp, vp, vp, vp,
                                        ctypes.c_size_t, vp]
     lib.pinn_balance_terms.restype = i32
+    lib.pinn_causal_state_bytes.argtypes = []
+    lib.pinn_causal_state_bytes.restype = ctypes.c_size_t
+    lib.pinn_causal_workspace_bytes.argtypes = [i64, i32]
+    lib.pinn_causal_workspace_bytes.restype = ctypes.c_size_t
+    lib.pinn_causal_init.argtypes = [vp, ctypes.c_size_t, ctypes.POINTER(f64), i32, f64, vp]
+    lib.pinn_causal_init.restype = i32
+    lib.pinn_causal_weights.argtypes = [vp, i64, vp, i64, i32, f64, f64, i32, vp, ctypes.c_size_t, vp, vp, vp, vp, vp, ctypes.c_size_t, vp]
+    lib.pinn_causal_weights.restype = i32
     u64 = ctypes.c_uint64
     lib.pinn_resample_workspace_bytes.argtypes = [i64]
     lib.pinn_resample_workspace_bytes.restype = ctypes.c_size_t
@@ -216,6 +228,7 @@ ABI_SYMBOLS = ('pinn_create', 'pinn_create_ex', 'pinn_destroy', 'pinn_layout', '
                'pinn_optim_step', 'pinn_optim_step_at', 'pinn_residual_optim_step', 'pinn_reduce_rows', 'pinn_last_reduce_kernel_name', 'pinn_port_probe',
                'pinn_lbfgs_ctrl_bytes', 'pinn_lbfgs_workspace_bytes', 'pinn_lbfgs_direction',
                'pinn_balance_state_bytes', 'pinn_balance_workspace_bytes', 'pinn_balance_init', 'pinn_balance_terms',
+               'pinn_causal_state_bytes', 'pinn_causal_workspace_bytes', 'pinn_causal_init', 'pinn_causal_weights',
                'pinn_resample_workspace_bytes', 'pinn_resample_points', 'pinn_resample_redraw',
                'pinn_last_error', 'pinn_backend')
 
@@ -595,6 +608,43 @@ class Net:
                 None if term_loss_out is None else ctypes.c_void_p(int(term_loss_out)),
                 None if weight_out is None else ctypes.c_void_p(int(weight_out)), _ptr(workspace), workspace.numel() * 8,
                 _stream(out) if stream is None else stream))
+
+    # ---- causal training weights (include/pinn.h pinn_causal_weights) -----------------------------------------------------------------
+    def causal_state(self, ladder, delta, device, state=None, stream=None):
+        """ the state block of pinn_causal_weights (float64 tensor) holding the tolerance ladder and delta, everything else zero """
+        if state is None:
+            state = torch.zeros(int(self.lib.pinn_causal_state_bytes()) // 8, dtype=torch.float64, device=device)
+        _check(state, 'state', torch.float64)
+        host = (ctypes.c_double * len(ladder))(*[float(e) for e in ladder])
+        with _on_device(state):
+            self._raise(self.lib.pinn_causal_init(_ptr(state), state.numel() * 8, host, len(ladder), float(delta),
+                                                  _stream(state) if stream is None else stream))
+        return state
+
+    def causal_workspace(self, n, bins, device):
+        need = int(self.lib.pinn_causal_workspace_bytes(int(n), int(bins)))
+        if need == 0:
+            raise ValueError(f'causal weights: n={n}, bins={bins} is outside the range of the kernels')
+        return torch.empty(need // 8, dtype=torch.float64, device=device)
+
+    def causal_weights(self, xs, time, r, bins, t_lo, t_hi, update, state, w_out, workspace, bin_weight_out=None, eps_out=None,
+                       mean_sq_out=None, stream=None):
+        """ w_out[:n] <- the causal weight of every point of the batch `xs` [n, d] (time column `time`) from the residuals `r` [n] (three
+        launches; include/pinn.h pinn_causal_weights). bin_weight_out / eps_out / mean_sq_out: device ADDRESSES (int) or None -- rows of
+        the caller's histories """
+        _check(xs, 'xs'); _check(r, 'r'); _check(w_out, 'w_out')
+        _check(state, 'state', torch.float64); _check(workspace, 'workspace', torch.float64)
+        if xs.dim() != 2 or not 0 <= int(time) < xs.shape[1]:
+            raise ValueError(f'xs must be [n, d] with the time column {time} inside it')
+        n, d = xs.shape
+        if r.numel() != n or w_out.numel() < n:
+            raise ValueError(f'r and w_out must hold one entry per point ({n})')
+        addr = lambda a: None if a is None else ctypes.c_void_p(int(a))
+        with _on_device(w_out):
+            self._raise(self.lib.pinn_causal_weights(
+                ctypes.c_void_p(xs.data_ptr() + 4 * int(time)), d, _ptr(r), n, int(bins), float(t_lo), float(t_hi), int(bool(update)),
+                _ptr(state), state.numel() * 8, _ptr(w_out), addr(bin_weight_out), addr(eps_out), addr(mean_sq_out), _ptr(workspace),
+                workspace.numel() * 8, _stream(w_out) if stream is None else stream))
 
     # ---- residual-adaptive resampler (include/pinn.h pinn_resample_points) -----------------------------------------------------------
     def resample_workspace(self, m, device):

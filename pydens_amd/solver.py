@@ -24,6 +24,7 @@ from tqdm import tqdm
 
 from . import engine, trace
 from .balance import LossBalancer
+from .causal import CausalWeights
 from .model import ConvBlockModel, InputProbe, PROBE
 from . import tokens
 from .tokens import current_model
@@ -443,6 +444,10 @@ class Solver:
         self.last_fit_balance = None        # fit(loss_weights=...): e.g. 'max_mean/fused', 'fixed/generic'; None: the plain sum of the terms
         self._balance = None                # the LossBalancer of the running / last weighted fit
         self._term_history, self._term_pending = [], []     # per weighted fit: (terms, losses [it, T], weights [it, T]) / the device histories
+        self.last_fit_causal = None         # fit(causal=...): e.g. 'bins32/generic'; None: the equation term is the plain mean
+        self._causal = None                 # the CausalWeights of the running / last causal fit
+        self._causal_run = None             # ... and, while its fit runs, where the running iteration's rows of the histories are
+        self._causal_history, self._causal_pending = [], []     # per causal fit: (weights [it, M], eps [it], mean r^2 [it]) / the device histories
         self.optimizer_refusal = None       # why the last `fit(optimizer='LBFGS')` under the 'fused' path kept torch.optim (None: it did not)
         if os.environ.get('PYDENS_AMD_OPTIMIZER'):
             self.set_optimizer_path(os.environ['PYDENS_AMD_OPTIMIZER'])
@@ -1340,10 +1345,70 @@ class Solver:
         `factory(optimizer) -> scheduler`; the torch loop `opt.step(); sched.step()` once per iteration, on every step path
         (`_set_scheduler`). `fit(optimizer=None)` carries the running schedule on; a new optimizer without one has a constant rate. """
         lr_scheduler, lr_scheduler_kwargs = kwargs.pop('lr_scheduler', None), kwargs.pop('lr_scheduler_kwargs', None)
-        loss_weights = kwargs.pop('loss_weights', None)
+        loss_weights, causal = kwargs.pop('loss_weights', None), kwargs.pop('causal', None)
         with self._device_guard():
             return self._fit(niters, batch_size, sampler, loss_terms, optimizer, criterion, lr, lr_scheduler, lr_scheduler_kwargs,
-                             loss_weights=loss_weights, **kwargs)
+                             loss_weights=loss_weights, causal=causal, **kwargs)
+
+    # ---- causal training weights ----------------------------------------------------------------------------------------------------
+    def _check_causal(self, causal, loss_terms, optimizer, criterion, lr, loss_weights, kwargs):
+        """ `fit(causal=...)`: every refusal, raised before the call has changed anything. Served: the generic step with nn.MSELoss(), one
+        process, an optimizer that steps once per batch. With `loss_weights` the combination is refused: the term rows would have to be
+        evaluated with the causal weights inside the 'equation' row and recorded once per iteration, which is code of its own. """
+        if not isinstance(causal, CausalWeights):
+            raise ValueError(f'causal={causal!r}: a CausalWeights object (or None)')
+        if 'equation' not in loss_terms:
+            raise ValueError(f"causal: the weights act on the equation term, and 'equation' is not among loss_terms={list(loss_terms)}")
+        if type(criterion) is not nn.MSELoss or criterion.reduction != 'mean':
+            raise NotImplementedError(f'causal: the weighted equation term is mean_i w_i r_i^2, the form of nn.MSELoss() with mean '
+                                      f'reduction; got {criterion!r}')
+        if self._steps_by_closure(optimizer, lr, kwargs):
+            raise NotImplementedError('causal: an optimizer that steps through a closure (L-BFGS) re-evaluates the batch inside one step, '
+                                      'and the weights and the tolerance ladder must not move under its line search')
+        if self._world()[1] > 1:
+            raise NotImplementedError('causal: under torch.distributed every rank would weight its share of the batch by its own bin sums; '
+                                      'the all-reduce of the bin sums is not built')
+        if loss_weights is not None:
+            raise NotImplementedError('causal: together with loss_weights -- the term rows of a weighted fit are evaluated apart, and the '
+                                      "causal weights inside the 'equation' row are not built; use one of the two")
+        resolved = causal.resolve(self.model)
+        if causal.state is not None and causal.state.device != self.device:
+            raise ValueError(f'causal: this CausalWeights lives on {causal.state.device}, the solver on {self.device}')
+        if self.custom_forward:
+            # (the bins are those of the batch's own time column: a forward() that hands the network another time is not followed)
+            devices = [self.device] if self.device.type == 'cuda' else []
+            with torch.random.fork_rng(devices=devices):
+                pts = torch.rand((64, self.model.total), device=self.device)
+                imap = self._input_map(pts)
+            if imap is not None and not torch.equal(imap[0][:, resolved[0]], pts[:, resolved[0]]):
+                raise NotImplementedError(f"causal: this model's forward() maps the time column {resolved[0]} before the network sees it; the "
+                                          'bins would be those of another time than the network is trained on')
+
+    @property
+    def causal_weight_history(self):
+        """ [iterations, M] float32: the bin weights w_k every iteration of the fits with `causal` was stepped with (those over the latest
+        number of bins), fetched lazily like `losses` """
+        return self._causal_stacked(1)
+
+    @property
+    def causal_eps_history(self):
+        """ [iterations] float32: the tolerance of each of those iterations """
+        return self._causal_stacked(2)
+
+    @property
+    def residual_mse_history(self):
+        """ [iterations] float32: the UNWEIGHTED mean r^2 of the equation term of each of those iterations (`losses` holds the weighted loss) """
+        return self._causal_stacked(3)
+
+    def _causal_stacked(self, which):
+        for bins, weight_hist, eps_hist, mse_hist, done in self._causal_pending:
+            self._causal_history.append((bins, ) + tuple(h[:done[0]].detach().cpu().numpy().copy() for h in (weight_hist, eps_hist, mse_hist)))
+        self._causal_pending = []
+        runs = self._causal_history
+        if not runs:
+            return np.zeros((0, 0) if which == 1 else (0, ), dtype=np.float32)
+        bins = runs[-1][0]
+        return np.concatenate([run[which] for run in runs if run[0] == bins], axis=0)
 
     # ---- loss-term weights ---------------------------------------------------------------------------------------------------------
     def _steps_by_closure(self, optimizer, lr, kwargs):
@@ -1548,9 +1613,14 @@ class Solver:
         self.lrs.append(rate)
 
     def _fit(self, niters, batch_size, sampler, loss_terms, optimizer, criterion, lr, lr_scheduler=None, lr_scheduler_kwargs=None,
-             loss_weights=None, **kwargs):
+             loss_weights=None, causal=None, **kwargs):
         model = self.model
         balance = None
+        if causal is not None:                  # (refusals first: the call has changed nothing yet)
+            self._check_causal(causal, loss_terms if isinstance(loss_terms, (tuple, list)) else (loss_terms, ), optimizer, criterion, lr,
+                               loss_weights, kwargs)
+            if optimizer is None and self.optimizer is None:
+                raise ValueError('optimizer=None reuses the optimizer of a previous fit call; there is none yet')
         if loss_weights is not None:            # (refusals first: the call has changed nothing yet)
             balance = self._resolve_loss_weights(loss_weights, loss_terms if isinstance(loss_terms, (tuple, list)) else (loss_terms, ),
                                                  self._steps_by_closure(optimizer, lr, kwargs))
@@ -1601,6 +1671,8 @@ class Solver:
         only_known_terms = all(term == 'equation' or 'constraint' in term for term in loss_terms)
         fused = (self.use_fused and crit is not None and not self.ic_trainable and only_known_terms and lowered
                  and len(loss_terms) > 0 and (self.program is not None or 'equation' not in loss_terms))
+        if causal is not None:
+            fused = False                       # (the weights multiply the residual between the two halves of the generic step)
         rank, world = self._world()
         if world > 1:
             self.begin_data_parallel()
@@ -1646,11 +1718,21 @@ class Solver:
             wb = dict(balance=balance, rows=self._term_rows(len(terms)), mask=mask, term_ptr=term_hist.data_ptr(), weight_ptr=weight_hist.data_ptr(),
                       nums=[None if term == 'equation' else int(term.replace('constraint', '').replace('_', '')) for term in terms],
                       keep=(term_hist, weight_hist))
+        self.last_fit_causal = None
+        if causal is not None:
+            causal.bind(model.net, model, local_batch, self.device)
+            hists = (torch.zeros((niters, causal.bins), dtype=torch.float32, device=self.device),
+                     torch.zeros(niters, dtype=torch.float32, device=self.device), torch.zeros(niters, dtype=torch.float32, device=self.device))
+            self._causal_pending.append((causal.bins, ) + hists + (done, ))
+            self._causal = causal
+            self.last_fit_causal = f'bins{causal.bins}/{self.last_fit_path}'
+            self._causal_run = dict(causal=causal, it=0, ptrs=tuple(h.data_ptr() for h in hists), keep=hists, stream=stream)
         try:
             self._fit_loop(niters, local_batch, sampler, loss_terms, nums_constraints, criterion, world, fused, one_launch,
                            flat_adam, stream, history, history_ptr, done, wb)
         finally:
             self._global_batch = None
+            self._causal_run = None
 
     def _fit_loop(self, niters, local_batch, sampler, loss_terms, nums_constraints, criterion, world, fused, one_launch,
                   flat_adam, stream, history, history_ptr, done, wb=None):
@@ -1663,6 +1745,8 @@ class Solver:
         by_closure = self.optimizer.needs_closure
         for it in tqdm(range(niters), disable=None):
             xs = self._sample(local_batch, sampler, stream)
+            if self._causal_run is not None:
+                self._causal_run['it'] = it         # (the row of the causal histories this iteration writes)
             rate = self._rate_begin()               # (a schedule: this iteration's learning rate, by value through the calls below)
             if by_closure:
                 # the batch is drawn ONCE; every closure call re-runs the gradient part of the iteration on it, and the iteration's loss is
@@ -1886,7 +1970,8 @@ class Solver:
         streams, an equation that takes torch gradients with respect to its inputs, a model subclass's own forward(): recording those
         ends in a crash inside hipStreamEndCapture on ROCm 7.2 (not an exception: tools/graph_crash_probe.py), so they are never tried. """
         model = self.model
-        ok = (world == 1 and not self.custom_forward and not self.needs_x_grad
+        # (a causal fit: pinn_causal_weights takes this iteration's rows of the histories and its `update` by value -- kept eager)
+        ok = (world == 1 and not self.custom_forward and not self.needs_x_grad and self._causal_run is None
               and not (model.initial_condition is not None and model.ic_constant is None))
         return self._graph_step(xs, ('generic', tuple(xs.shape), id(criterion), id(self._eq), tuple(loss_terms)),
                                 lambda pts: self._generic_step(pts, loss_terms, nums_constraints, criterion, world), enabled=ok,
@@ -2016,7 +2101,17 @@ class Solver:
                 if model.initial_condition is not None and model.ic_constant is None and not self.custom_forward:
                     ic_streams = self._ic_streams(xs, create_graph=True)       # (custom forward(): the IC is torch code of the model)
                 r = self._eval_equation(leaf, xs, ic_streams)
-                term = criterion(r, torch.zeros_like(xs[:, :1]))                        # :448
+                run = self._causal_run if probe is None else None
+                if run is not None:
+                    # causal weights of this batch from its own residuals (three launches, include/pinn.h pinn_causal_weights), held
+                    # constant under the gradient: the equation term is mean_i w_i r_i^2
+                    it, ptrs = run['it'], run['ptrs']
+                    w = run['causal'].point_weights(model.net, xs, r.detach().reshape(-1).float().contiguous(),
+                                                    bin_weight_out=ptrs[0] + 4 * run['causal'].bins * it, eps_out=ptrs[1] + 4 * it,
+                                                    mean_sq_out=ptrs[2] + 4 * it, stream=run['stream'])
+                    term = (w.view_as(r) * r * r).mean()
+                else:
+                    term = criterion(r, torch.zeros_like(xs[:, :1]))                        # :448
                 loss = loss + (term if world == 1 else term * w_eq)
 
             calls = []          # model calls of the constraint terms that carry derivative streams (_model_at)
